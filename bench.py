@@ -4,14 +4,23 @@ on synthetic two-stream decks, N GPUs of one node, one process per GPU.
 
     python bench.py                      # BASELINE.json configs[2]: 256^3 two-stream, 2 species x 64 ppc -- the deck the
                                          # north star's targets are quoted on (>= 0.50 of roofline at 64 ppc, strong scaling
-                                         # 1 -> 8 GPUs), on ONE GPU; a short run of configs[1] (128^3, 32 ppc) rides along
+                                         # 1 -> 8 GPUs), on ONE GPU; with --full a short run of configs[1] (128^3, 32 ppc) rides along
     python bench.py --config 1           # configs[1] alone
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   # the SAME 256^3 box in N x-slabs
 
 Prints ONE JSON line on rank 0.  `value` = particle pushes per second of the whole job over K
-full steps (sort included when due); `roofline` prices the advance_p kernel alone against HBM;
-`cpu_baseline` is the reference's own executable under mpiexec (the oracle port when that binary
-is not there) on the box's host cores, one 24^3 block of the same deck per core, for about 10 s.
+full steps (sort included when due); `roofline` prices the advance_p kernel alone against HBM (from
+the timed steps' own launches).  A plain run does only that: set-up, warm-up, the K timed steps.
+
+    --full               everything else the benchmark measures and checks: the run's particle / energy
+                         census, and at N = 1 on the default deck the ride-along runs (the other advance_p
+                         arithmetic, sort interval 20, configs[1], the configs[3] slab, the heated phase,
+                         configs[4], the C++ deck host) and `cpu_baseline` -- the reference's own executable
+                         under mpiexec (the oracle port when that binary is not there) on the box's host
+                         cores, one 24^3 block of the same deck per core, for about 10 s
+    --dump-outputs DIR   after the timed steps, what they computed (fields and the particles' moments at a
+                         fixed, seeded sample of voxels) as DIR/*.npy, for comparing two builds output for
+                         output (dump_outputs)
 """
 import argparse
 import importlib
@@ -206,6 +215,46 @@ def workload_name(d, args, world):
             + (f", vth={args.vth}" if args.vth is not None else ""))
 
 
+DUMP_FIELDS = ("ex", "ey", "ez", "cbx", "cby", "cbz", "jfx", "jfy", "jfz")
+DUMP_HYDRO = ("jx", "jy", "jz", "rho", "px", "py", "pz", "ke", "txx", "tyy", "tzz", "tyz", "tzx", "txy")
+
+
+def dump_outputs(engine, d, out_dir, prefix=""):
+    """--dump-outputs: the state the timed steps left, as a caller of the step reads it back, at a fixed seeded sample of the
+    interior voxels (the whole of it is 10^2 GB at the default deck; these files stay under 64 MB).  Every file has the same
+    shape in every run of the same arguments, and no value depends on the order of the particle array (the float atomics'
+    order on the device) beyond float rounding:
+      fields.npy              float32 [voxels, 9]: DUMP_FIELDS
+      hydro<k>.npy            float32 [voxels, 14]: DUMP_HYDRO of species k, the moments of a hydro dump (hydro_p.c:24-176 +
+                              synchronize_hydro): every particle spread over the 8 nodes of its cell with trilinear weights,
+                              so a particle that ends a rounding error away on the other side of a face moves them by that
+                              error, not by a whole particle
+      species_summary.npy     float64 [species, 2]: live particles, kinetic energy (energy_p)
+    At N > 1 every rank writes its own domain's, named rank<r>_*.npy (moments on faces shared with other ranks: this rank's
+    part).  Call it after everything else has read the engine: the moments may sort the species."""
+    L = importlib.import_module("old-vpic_amd.layout")
+    os.makedirs(out_dir, exist_ok=True)
+    g = engine.grid
+    nx, ny, nz = int(g.nx), int(g.ny), int(g.nz)
+    n_species = len(d["species"])
+    interior = nx * ny * nz
+    size = min(interior, (56 << 20) // (4 * (len(DUMP_FIELDS) + len(DUMP_HYDRO) * n_species)))
+    pick = np.sort(np.random.default_rng(20240611).choice(interior, size=size, replace=False))
+    vox = L.voxel(pick % nx + 1, (pick // nx) % ny + 1, pick // (nx * ny) + 1, nx, ny, nz)
+    f = engine.get_fields()[vox]
+    np.save(os.path.join(out_dir, prefix + "fields.npy"), np.stack([f[c] for c in DUMP_FIELDS], axis=1).astype(np.float32))
+    del f
+    summary = np.zeros((n_species, 2), np.float64)
+    for sp in range(n_species):
+        summary[sp] = engine.np(sp), engine.energy_p(sp)
+        engine.clear_hydro()
+        engine.accumulate_hydro_p(sp)
+        engine.synchronize_hydro()
+        h = engine.get_hydro()[vox]
+        np.save(os.path.join(out_dir, prefix + "hydro%d.npy" % sp), np.stack([h[c] for c in DUMP_HYDRO], axis=1).astype(np.float32))
+    np.save(os.path.join(out_dir, prefix + "species_summary.npy"), summary)
+
+
 def run_workload(args, d, world, rank, local_rank, steps, warmup):
     """Load the deck, do `warmup` untimed steps, time exactly `steps` steps between barriers; returns the
     measurements of this rank reduced over the job (elapsed = max over ranks)."""
@@ -259,8 +308,8 @@ def run_workload(args, d, world, rank, local_rank, steps, warmup):
     for _ in range(warmup):
         stepper(step)
         step += 1
-    # the run checks itself, outside the timed region: particle count and total energy (kinetic of every species + field)
-    # before and after the timed steps (energy_p.cxx:124-157, energy_f.c:139-179)
+    # --full: the run checks itself, outside the timed region: particle count and total energy (kinetic of every species +
+    # field) before and after the timed steps (energy_p.cxx:124-157, energy_f.c:139-179)
     n_species = len(d["species"])
 
     def census():
@@ -270,7 +319,7 @@ def run_workload(args, d, world, rank, local_rank, steps, warmup):
             return dict(particles=int(t.item()))
         kin = [engine.energy_p(sp) for sp in range(n_species)]
         return dict(particles=int(sum(engine.np(sp) for sp in range(n_species))), kinetic=float(sum(kin)), field=float(engine.energy_f().sum()))
-    check_before = census()
+    check_before = census() if args.full else None
     engine.profile_enable(True)
     if dom is not None:
         dom.trace_reset(True)
@@ -292,11 +341,13 @@ def run_workload(args, d, world, rank, local_rank, steps, warmup):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    check_after = census()
-    check = dict(before=check_before, after=check_after, particles_conserved=check_before["particles"] == check_after["particles"])
-    if hasattr(engine, "species_stats"):
-        check["species"] = [engine.species_stats(sp) for sp in range(n_species)]
-    if "kinetic" in check_before:
+    check = None
+    if args.full:
+        check_after = census()
+        check = dict(before=check_before, after=check_after, particles_conserved=check_before["particles"] == check_after["particles"])
+        if hasattr(engine, "species_stats"):
+            check["species"] = [engine.species_stats(sp) for sp in range(n_species)]
+    if check is not None and "kinetic" in check_before:
         e0, e1 = check_before["kinetic"] + check_before["field"], check_after["kinetic"] + check_after["field"]
         check.update(total_energy_drift=(e1 - e0) / e0 if e0 else None, steps=steps,
                      note="energies in the deck's units, rank-local; the two-stream instability moves kinetic into field energy, the sum drifts at the 1e-4 level per 20 steps")
@@ -337,6 +388,8 @@ def run_workload(args, d, world, rank, local_rank, steps, warmup):
         t = torch.tensor([exchange[k] for k in keys], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         exchange["max_over_ranks"] = {k: float(v) for k, v in zip(keys, t.tolist())}
+    if args.dump_outputs:
+        dump_outputs(engine, d, args.dump_outputs, "" if world == 1 else "rank%d_" % rank)
     engine.close()
     del engine, dom
     torch.cuda.empty_cache()
@@ -404,6 +457,10 @@ def main():
                          "particles in z, 128x128x64 cells")
     ap.add_argument("--topology", type=int, nargs=3, default=None, help="domains along x y z (default: x-slabs, N 1 1)")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL over xGMI) or gloo (one-GPU rehearsal, host-staged)")
+    ap.add_argument("--full", action="store_true", help="also the census check, the ride-along runs and cpu_baseline (a plain run "
+                    "only sets up, warms up and times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed (fields and particle moments at a fixed, seeded sample of voxels) as DIR/*.npy")
     args = ap.parse_args()
 
     import torch
@@ -437,33 +494,35 @@ def main():
     c3 = None
     r = run_workload(args, d, world, rank, local_rank, args.steps, args.warmup)
     other = None
-    if world == 1 and default_deck and not args.no_second_config:
+    if world == 1 and default_deck and args.full and not args.no_second_config:
         # the same deck with the other arithmetic of advance_p (include/vpic_hip.h: exact is the engine's default and the
         # headline; fast = contracted multiply-adds and 1-ulp rsq / rcp, momenta within 8 ulp), a short run
         a2 = argparse.Namespace(**vars(args))
         a2.push = "fast" if args.push == "exact" else "exact"
+        a2.dump_outputs = None                             # (the outputs are the headline run's)
         r2 = run_workload(a2, d, 1, rank, local_rank, 10, 5)
         other = {"push_arithmetic": a2.push, "value": r2["total_np"] * 10 / r2["elapsed"], "steps": 10, "warmup": 5,
                  "ms_per_step": r2["elapsed"] / 10 * 1e3, "advance_p_pushes_per_s": r2["kernel_rate"], "roofline": r2["roofline"]}
 
     si20 = None
-    if world == 1 and default_deck and not args.no_second_config and args.sort_interval != 20:
+    if world == 1 and default_deck and args.full and not args.no_second_config and args.sort_interval != 20:
         # SURVEY.md 8d quotes the metric with sort_interval = 20; the headline keeps 10 (what rounds 1-2 reported), this block is
         # the same deck sorted every 20 steps (round 3: the tile windows follow the beams between sorts, and the two intervals
         # come out within 2 % of each other)
         a3 = argparse.Namespace(**vars(args))
         a3.sort_interval = 20
+        a3.dump_outputs = None
         d3 = deck(a3, 1)
         r3 = run_workload(a3, d3, 1, rank, local_rank, 40, 5)      # (two whole sort cycles, like the headline's 20 steps at interval 10)
         si20 = {"workload": workload_name(d3, a3, 1), "value": r3["total_np"] * 40 / r3["elapsed"], "steps": 40, "warmup": 5,
                 "ms_per_step": r3["elapsed"] / 40 * 1e3, "ms_per_step_median": r3["median_ms"],
                 "advance_p_pushes_per_s": r3["kernel_rate"], "roofline": r3["roofline"]}
-    if world == 1 and default_deck and not args.no_second_config:
+    if world == 1 and default_deck and args.full and not args.no_second_config:
         # Two smaller decks ride along, each in a FRESH PROCESS started once this one has released its engines: in one process,
         # whichever deck runs second pays for the first one's freed memory (behind the 137 GB deck the 128^3 deck's kernel took
         # 1.8 x as long; ahead of it, the small decks cost the large one 1.5-2 %: profiles/r03_* of round 3).
         def rider(extra):
-            cmd = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-second-config", "--push", args.push,
+            cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-second-config", "--push", args.push,
                    "--accumulation", args.accumulation, "--device-warmup-s", "0"] + extra      # (the device is warm by now)
             res = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
             for line in reversed(res.stdout.splitlines()):
@@ -489,7 +548,7 @@ def main():
               "advance_p_pushes_per_s": j4["advance_p_pushes_per_s"], "roofline": j4["roofline"], "advance_p_by_species": j4.get("advance_p_by_species"),
               "note": "advance_p figures average over the 2 charged species and their 2 charge-0 tracer copies (which deposit nothing)"}
     deck_host = None
-    if world == 1 and default_deck and not args.no_second_config:
+    if world == 1 and default_deck and args.full and not args.no_second_config:
         # configs[1] through the DECK API: oracle/decks/twostream.cxx (the very file cpu_baseline runs on the reference's
         # build) compiled against the C++ deck host with -DTS_N=128 (old-vpic_amd/host/twostream128.hip.exe, built by
         # __graft_entry__.build()): begin_initialization loads the particles on the host, vpic_simulation::advance runs on the GPU
@@ -513,14 +572,14 @@ def main():
             except Exception as exc:                       # noqa: BLE001
                 rider_errors.append("deck_host: %s" % str(exc)[-300:])
     sustained = None
-    if world == 1 and default_deck and not args.no_second_config:
+    if world == 1 and default_deck and args.full and not args.no_second_config:
         # the headline times steps 5..25 of the deck -- its quiet phase.  The two-stream instability heats the beams from about
         # step 100 on (more cell crossings, deposits further from their tiles): steps 160..200 of the same deck, a fresh process
         j5 = try_rider(["--steps", "40", "--warmup", "160"])
         if j5: sustained = {"workload": j5["config"]["workload"], "value": j5["value"], "steps": 40, "warmup": 160, "ms_per_step": j5["ms_per_step"],
                             "advance_p_pushes_per_s": j5["advance_p_pushes_per_s"], "roofline": j5["roofline"], "check": j5.get("check")}
     drift512 = None
-    if world == 1 and default_deck and not args.no_second_config:
+    if world == 1 and default_deck and args.full and not args.no_second_config:
         # BASELINE configs[4] (the deposition-bound stress: cold uniform drift, 1 species x 512 ppc) at 128^3 -- the per-GPU
         # particle count of the 256^3 deck on 8 GPUs (2^30), one launch segment short of the 2^30 limit
         j6 = try_rider(["--deck", "drift", "--grid", "128", "128", "128", "--ppc", "512", "--steps", "10", "--warmup", "3"])
@@ -548,13 +607,14 @@ def main():
             "advance_p_pushes_per_s": r["kernel_rate"],
             "full_step_ns_per_particle": r["elapsed"] / args.steps / r["total_np"] * 1e9,
             "roofline": r["roofline"],
-            "check": r["check"],
         }
+        if r["check"] is not None:
+            out["check"] = r["check"]
         if r["sorting"] is not None:
             out["advance_p_sorting"] = r["sorting"]
         if r["by_species"]:
             out["advance_p_by_species"] = r["by_species"]
-        if world == 1 and default_deck and not args.no_second_config and rider_errors:
+        if world == 1 and default_deck and args.full and not args.no_second_config and rider_errors:
             out["riders_failed"] = rider_errors
         if r["host_syncs"] is not None:
             out["host_syncs_per_step"] = r["host_syncs"]
@@ -579,7 +639,7 @@ def main():
         if other:
             out["same_deck_" + other["push_arithmetic"] + "_arithmetic"] = other
             out["roofline_" + other["push_arithmetic"]] = other["roofline"]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(d)
         print(json.dumps(out))
     if world > 1:

@@ -93,10 +93,10 @@ def test_struct_mirrors():
     assert C.sizeof(eng.GridDesc) == 4 * (4 + 6 + 3 + 12 + 1)
 
 
-def test_headers_compile_as_c():
+def test_headers_compile_as_c(tmp_path):
     import subprocess
     src = '#include "vpic_hip_dropin.h"\nint main(void){return sizeof(vpic_grid_t)==240?0:1;}\n'
-    exe = "/tmp/vpic_hip_hdr_test"
+    exe = str(tmp_path / "vpic_hip_hdr_test")
     subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe],
                    input=src.encode(), check=True)
     subprocess.check_call([exe])

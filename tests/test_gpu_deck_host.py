@@ -14,10 +14,19 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def lib_env(env=None):
+    """The environment for an executable linked against libvpic_hip.so: this tree's library first on the loader's path, so
+    that the executable finds it wherever it lies (oracle/_ref/ may have been built in another copy of the tree)."""
+    env = dict(os.environ if env is None else env)
+    env["LD_LIBRARY_PATH"] = os.pathsep.join(d for d in (os.path.join(ROOT, "old-vpic_amd"), env.get("LD_LIBRARY_PATH")) if d)
+    return env
+
+
 def run_deck(cmd, **kw):
     """subprocess.check_call for a deck executable with its output kept out of the test log -- unless the run fails: then
     the tail of what it wrote is the assertion message."""
     kw.pop("stdout", None); kw.pop("stderr", None)
+    kw["env"] = lib_env(kw.get("env"))
     r = subprocess.run([str(c) for c in cmd], capture_output=True, text=True, **kw)
     assert r.returncode == 0, "%s -> exit %d\n%s" % (" ".join(str(c) for c in cmd[:4]), r.returncode, (r.stderr or "")[-3000:])
     return r

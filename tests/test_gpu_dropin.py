@@ -12,6 +12,14 @@ from conftest import bits_equal
 pytestmark = pytest.mark.gpu
 
 
+def lib_env():
+    """The environment for an executable linked against libvpic_hip.so: this tree's library first on the loader's path, so
+    that the executable finds it wherever it lies (oracle/_ref/ may have been built in another copy of the tree)."""
+    import os
+    lib_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "old-vpic_amd")
+    return dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(d for d in (lib_dir, os.environ.get("LD_LIBRARY_PATH")) if d))
+
+
 @pytest.fixture(scope="module")
 def D():
     d = importlib.import_module("old-vpic_amd.dropin")
@@ -230,7 +238,7 @@ def test_the_reference_itself_on_the_dropin_library(tmp_path, variant):
     if not os.path.exists(exe):
         pytest.skip("the drop-in executables are built where /root/reference is (python -c 'import __graft_entry__ as g; g.build()')")
     importlib.import_module("old-vpic_amd").lib()
-    subprocess.check_call([exe, "-tpp=1"], cwd=tmp_path, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
+    subprocess.check_call([exe, "-tpp=1"], cwd=tmp_path, env=lib_env(), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
     gold = np.load(os.path.join(ROOT, "tests", "golden", "deck16.npz"))
     key = {"": "energies_1rank", "_clean": "clean_energies_1rank", "_mat": "mat_energies_1rank", "_abs": "abs1_energies"}[variant]
     en, ref = np.loadtxt(tmp_path / "energies16.txt"), gold[key]
@@ -265,7 +273,7 @@ def test_the_reference_itself_on_two_ranks(tmp_path, variant):
     if not os.path.exists(exe) or not os.path.exists(mpiexec):
         pytest.skip("the drop-in executables are built where /root/reference is; mpiexec comes with the image")
     importlib.import_module("old-vpic_amd").lib()
-    subprocess.check_call([mpiexec, "-n", "2", exe, "-tpp=1"], cwd=tmp_path, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
+    subprocess.check_call([mpiexec, "-n", "2", exe, "-tpp=1"], cwd=tmp_path, env=lib_env(), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
     gold = np.load(os.path.join(ROOT, "tests", "golden", "deck16.npz"))
     en, ref = np.loadtxt(tmp_path / "energies16.txt"), gold["energies_2rank" if variant == "" else "abs2_energies"]
     assert en.shape[0] == 51
@@ -292,7 +300,7 @@ def test_the_reference_itself_sheet_deck_with_tracers(tmp_path):
     if not os.path.exists(exe):
         pytest.skip("the drop-in executables are built where /root/reference is")
     importlib.import_module("old-vpic_amd").lib()
-    subprocess.check_call([exe, "-tpp=1"], cwd=tmp_path, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
+    subprocess.check_call([exe, "-tpp=1"], cwd=tmp_path, env=lib_env(), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
     gold = np.load(os.path.join(ROOT, "tests", "golden", "sheet4.npz"))
     en, ref = np.loadtxt(tmp_path / "energies4.txt"), gold["n1_energies"]
     np.testing.assert_allclose(en[:, 7:], ref[:, 7:], rtol=2e-5)
@@ -314,7 +322,7 @@ def test_the_reference_itself_binary_dumps(tmp_path):
     if not os.path.exists(exe):
         pytest.skip("the drop-in executables are built where /root/reference is")
     importlib.import_module("old-vpic_amd").lib()
-    subprocess.check_call([exe, "-tpp=1"], cwd=tmp_path, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
+    subprocess.check_call([exe, "-tpp=1"], cwd=tmp_path, env=lib_env(), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
     gold = np.load(os.path.join(ROOT, "tests", "golden", "deck16.npz"))
     L = importlib.import_module("old-vpic_amd.layout")
     nh = len(gold["dump_fields16_head"])

@@ -3,7 +3,7 @@
 #   tools/final_profiles.sh <round tag, e.g. r01>
 cd "$(dirname "$0")/.."
 T=${1:-r01}; O=gpurun_out/final; mkdir -p $O
-python bench.py > $O/${T}_bench.json 2> $O/bench.err && tail -1 $O/${T}_bench.json | cut -c1-300
+python bench.py --full > $O/${T}_bench.json 2> $O/bench.err && tail -1 $O/${T}_bench.json | cut -c1-300
 bash tools/prof_stats.sh $T > $O/prof_stats.txt 2>&1 && cp gpurun_out/${T}_kernel_stats.csv $O/${T}_bench_kernel_stats.csv && tail -16 $O/prof_stats.txt
 bash tools/pmc_traffic.sh $T > $O/pmc_traffic.txt 2>&1 && cp gpurun_out/traffic_${T}_raw.json $O/${T}_traffic_raw.json && tail -8 $O/pmc_traffic.txt
 python bench.py --no-cpu-baseline --ppc 64 > $O/${T}_bench_ppc64.json 2>> $O/bench.err

@@ -2,7 +2,7 @@
 # the measurements behind profiles/r03_* and DESIGN.md section 5 (one GPU box):  tools/r03_profiles.sh
 cd "$(dirname "$0")/.."; ulimit -c 0; export VPIC_HIP_NO_REBUILD=1
 O=gpurun_out/r03p; mkdir -p $O
-python bench.py > $O/r03_bench.json 2> $O/bench.err && tail -1 $O/r03_bench.json | cut -c1-300
+python bench.py --full > $O/r03_bench.json 2> $O/bench.err && tail -1 $O/r03_bench.json | cut -c1-300
 echo "-- kernel stats"
 bash tools/prof_stats.sh r03 > $O/prof_stats.txt 2>&1 && cp gpurun_out/r03_kernel_stats.csv $O/r03_bench_kernel_stats.csv && tail -18 $O/prof_stats.txt
 bash tools/prof_stats.sh r03c1 --config 1 > $O/prof_stats_c1.txt 2>&1 && cp gpurun_out/r03c1_kernel_stats.csv $O/r03_config1_kernel_stats.csv

@@ -3,7 +3,7 @@
 # RCCL refuses two ranks on one device; the RCCL transport itself is tested with self-sends (tests/test_gpu_rccl_host.py)
 cd "$(dirname "$0")/.."; ulimit -c 0; export VPIC_HIP_NO_REBUILD=1 VPIC_HIP_SINGLE_DEVICE=1
 O=gpurun_out/r04n2; mkdir -p $O
-run() { timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $1 bench.py --gpus 2 --backend gloo --no-cpu-baseline "${@:2}" 2> $O/err_$1.txt | tail -1 | python -c "
+run() { timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $1 bench.py --full --gpus 2 --backend gloo --no-cpu-baseline "${@:2}" 2> $O/err_$1.txt | tail -1 | python -c "
 import json,sys
 j=json.loads(sys.stdin.readline())
 print('  %.2f G pushes/s  %.2f ms/step  transport %s  check %s' % (j['value']/1e9, j['ms_per_step'], j.get('transport'), {k: v for k, v in (j.get('check') or {}).items() if k in ('particles_conserved',)}))
