@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 #include "vpic_hip.h"
+#include "policy.h"
 
 namespace vpichip {
 
@@ -91,21 +92,13 @@ struct Species {
   int64_t n_holes = 0;
   ParticlesK p{}, aux{};             // aux: second buffer for the out-of-place sort
   DrainParams *drain_k = nullptr;
-  // adaptive sorting (vpic_hip_step, sort_interval < 0): events around the last push [0,1] and sort [2,3],
-  // cost of a sort, and sum / number of the push times since the last sort (ms)
+  // adaptive sorting (vpic_hip_step, sort_interval < 0): events around the last push [0,1] and sort [2,3]
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool push_timed = false, sort_timed = false, sorted_once = false;
-  double t_sort = 0, t_sum = 0; int n_push = 0;
+  bool push_timed = false, sort_timed = false;
+  Policy pol;                        // what the sort and push decisions remember (policy.h)
   int64_t *tag = nullptr, *tag2 = nullptr, *tag_aux = nullptr, *tag2_aux = nullptr;
   bool has_tags = false;             // tags all zero until a non-zero one is uploaded
-  double t_last = 0, growth_first = 0; int n_cycle = 0;   // adaptive sorting: see sort_due
-  // (one set per sort flavour, see flavour_cost: [0] by cell within a tile or by voxel, [1] by tile only)
-  double t_hist[2][32] = {{0}}; int n_hist[2] = {0, 0};                // ... the push times of earlier cycles by position in the cycle
-  double s_hist[2][33] = {{0}}; int sorted_after = 0;          // ... what a sort cost after n pushes (more steps, more disorder), pushes before the last sort
-  double c_hist[2][34] = {{0}}; double prev_sum = 0;           // ... measured cost per step (sort included) of whole cycles of n pushes; push time of the last whole cycle
-  bool wide_window = false;          // advance_p instance with the double-precision LDS window (crossing-heavy species; push.hip)
-  unsigned *crossed_dev = nullptr, *crossed_host = nullptr, *crossed_host_dev = nullptr;   // particles that left their cell in the last advance_p (device word, pinned mirror)
-  int64_t np_pushed_last = 0;        // particles of the previous advance_p launch (denominator of the crossing fraction)
+  unsigned *crossed_dev = nullptr, *crossed_host = nullptr, *crossed_host_dev = nullptr;   // per-launch counters (device shards; the pinned words, policy.h: PinnedWord)
   bool chargeless = false;           // every particle has q == 0 (tracer copies): advance_p skips all deposition
   vpic_particle_mover_t *pm = nullptr;
   int *nm_dev = nullptr;             // this species' mover counter in Engine::counters
@@ -127,33 +120,20 @@ struct Species {
   // the push before it (hist_valid) moves nothing: k_sort_p sets fuse_pending, and the next k_advance_p writes every particle
   // it pushes to its SORTED place in the second buffer -- places from the scan of hist[] (tpart2: where every key begins in
   // the new order; Engine::sort_next: the cursors) -- then swaps the buffers.  The order is that of the cells BEFORE that
-  // push (what hist[] counted).  crossed_host[2]: cursors that did not end where the next key begins (0 when the counts
+  // push (what hist[] counted).  crossed_host[PW_SORT_CHECK]: cursors that did not end where the next key begins (0 when the counts
   // matched the array; checked by the species' next push, which fails loudly otherwise).
   int *tpart2 = nullptr; int64_t tpart2_count = 0; bool fuse_pending = false;
   bool phase_pending = false;        // vpic_hip_advance_p_phase: the first launch ran, the interior tiles are still to be pushed
   bool tile_valid = false, adaptive = false;   // adaptive: the engine's own policy asks for the sorts (vpic_hip_sort_due)
   int64_t n_sorted = 0;
-  double cross_frac = 0;          // fraction of the particles that left their cell in the last advance_p (one launch behind)
   bool coarse_sorted = false;     // the last tile sort was by tile only
-  bool coarse_order = false;      // tile sorts group this species by tile only (particles.hip)
-  // ... chosen by measurement when the engine's sort policy times the cycles: cost per step of whole cycles in either
-  // flavour ([0] by cell within a tile, [1] by tile only; 0 = not on record), cycles since the flavour last changed
-  double flavour_cost[2] = {0, 0}; int flavour_cycles = 0;
-  // ... inside the push or before it: decided by MEASUREMENT (engine.hip: sort_and_push).  A species whose cells move as one (cold
-  // beams) lands in its new order in long runs and the sorting launch beats sort + push (29.7 ms against 20 + 16.8 at 256^3 x
-  // 64 ppc); one whose particles have spread (the same deck from step ~120 on) writes runs of two and loses (60 against 20 +
-  // 18.5).  ms of this species' sort + push in either way (0: not on record), the pair of events of the measurement under way
-  float sort_push_ms[2] = {0, 0}; hipEvent_t sp_ev[2] = {nullptr, nullptr}; int sp_kind = -1; bool sp_last = true;
-  // ... and of the push that counted for the sort (the last, slowest plain launch of the cycle): the yardstick that says whether
-  // sorting before the push is worth a first try -- 20 + 17 ms against 27-30 inside the push where the counting launch took
-  // 17.6 (ratio 1.6: no), 20 + 18.5 against 60 where it took 24 (2.5: yes)
-  float hint_push_ms = 0; hipEvent_t hp_ev[2] = {nullptr, nullptr}; bool hp_pending = false;
-  int64_t early_sorts = 0;        // sorts vpic_hip_step made ahead of a fixed interval because the deposits had begun to miss the windows
-  bool tile_unbalanced = false;   // the fullest tile alone would keep its workgroup busy several times longer than a balanced launch takes
+  // the pairs of events of the measurements of Policy::sort_push_ms (sp_kind: which one is under way) and hint_push_ms
+  hipEvent_t sp_ev[2] = {nullptr, nullptr}; int sp_kind = -1;
+  hipEvent_t hp_ev[2] = {nullptr, nullptr}; bool hp_pending = false;
 };
 
 // tiles of TILE_EDGE^3 cells over the interior (the last one of an axis may be partial)
-constexpr int TILE_EDGE = 4, TILE_CELLS = TILE_EDGE * TILE_EDGE * TILE_EDGE;
+constexpr int TILE_CELLS = TILE_EDGE * TILE_EDGE * TILE_EDGE;
 struct TileK {
   int sy, sz, ntx, nty, ntz, ntiles;
   unsigned mul_sy, sh_sy, mul_sz, sh_sz;     // magic_div of the voxel strides
@@ -331,7 +311,7 @@ int k_energy_p(Engine *e, Species &s, double *energy);
 int k_center_p(Engine *e, Species &s, bool uncenter);
 int k_sort_p(Engine *e, Species &s, bool tile_order = false, bool may_fuse = false);   // may_fuse: the caller pushes the species next (see Species::fuse_pending)
 int k_sort_scan(Engine *e, const int *counts, int *starts, int n1);                  // exclusive scan of counts[0..n1) into starts[] and Engine::sort_next[]
-int k_sort_check(Engine *e, Species &s, const int *starts, int n1);                    // every cursor ended where the next key begins? (crossed_host[2]; the next push fails loudly otherwise)
+int k_sort_check(Engine *e, Species &s, const int *starts, int n1);                    // every cursor ended where the next key begins? (PW_SORT_CHECK; the next push fails loudly otherwise)
 int k_sort_finish(Engine *e, Species &s, bool tile_order, bool coarse);                // what follows a sort's scatter (buffers swapped, bookkeeping)
 int k_tail_sort(Engine *e, Species &s);
 int k_measure_disorder(Engine *e, Species &s, int slot);

@@ -345,11 +345,12 @@ int vpic_hip_species_create(vpic_hip_engine_t *e, float q_m, int64_t max_np, int
   s.nm_dev = e->counters + (e->species.size() < (size_t)MAX_SPECIES ? C_NMS + (int)e->species.size() : C_NM);
   d.pm = s.pm; d.nm_counter = s.nm_dev;
   if (hipMalloc(&s.crossed_dev, sizeof(unsigned) * 256 * 16) != hipSuccess || hipMemset(s.crossed_dev, 0, sizeof(unsigned) * 256 * 16) != hipSuccess ||
-      hipHostMalloc(&s.crossed_host, sizeof(unsigned) * 8, hipHostMallocMapped) != hipSuccess ||   // [0] crossers of the last push, [1] particles of the fullest tile at the last tile sort, [2] see Species::fuse_pending, [3] runs that missed the tile windows in the last push, [4] the sort cycle that push belonged to
+      hipHostMalloc(&s.crossed_host, sizeof(unsigned) * 8, hipHostMallocMapped) != hipSuccess ||   // the pinned words (policy.h: PinnedWord)
       hipHostGetDevicePointer((void **)&s.crossed_host_dev, s.crossed_host, 0) != hipSuccess) {
     set_error("out of memory for a species counter"); return -1;
   }
-  s.crossed_host[0] = 0; s.crossed_host[1] = 0; s.crossed_host[2] = 0; s.crossed_host[3] = 0; s.crossed_host[4] = ~0u;
+  for (int w = PW_CROSSERS; w < PW_CYCLE; w++) s.crossed_host[w] = 0;
+  s.crossed_host[PW_CYCLE] = ~0u;
   (void)hipDeviceSynchronize();                          // the fill above ran on the null stream; the engine's stream does not wait for that one
   if (hipMalloc(&s.drain_k, sizeof(d)) != hipSuccess || hipMemcpy(s.drain_k, &d, sizeof(d), hipMemcpyHostToDevice) != hipSuccess) {
     set_error("out of device memory for a species record"); return -1;
@@ -499,7 +500,7 @@ int vpic_hip_debug_set_ablate(vpic_hip_engine_t *e, int bits) { ENGINE(e); e->kn
 int vpic_hip_debug_poke_tile_max(vpic_hip_engine_t *e, int sp, unsigned value) {
   ENGINE(e); SPECIES(e, sp);
   if (!e->species[sp].crossed_host) VH_FAIL("no counter word");
-  e->species[sp].crossed_host[1] = value;
+  e->species[sp].crossed_host[PW_FULLEST_TILE] = value;
   return 0;
 }
 int vpic_hip_species_get_tile_partition(vpic_hip_engine_t *e, int sp, int32_t *tpart, int64_t *count) {
@@ -549,6 +550,12 @@ int vpic_hip_set_push_mode(vpic_hip_engine_t *e, int mode) {
 // deposit -- twelve times the time of a tiled launch.  A species that lost the tile order to a sort by voxel (the per-voxel
 // moment kernels of a hydro dump or a cleaning step ask for one) is put back into it before it is pushed.
 static bool wants_tile_order(const Engine *e, const Species &s);
+// ms between a pair of events, or -1 while the second has not completed (wait: until it has) or the time cannot be read
+static float event_ms(const hipEvent_t ev[2], bool wait = false) {
+  float ms = 0;
+  if ((wait ? hipEventSynchronize(ev[1]) : hipEventQuery(ev[1])) != hipSuccess || hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess) return -1;
+  return ms;
+}
 static int order_for_deterministic_push(Engine *e, Species &s) {
   if (e->det_acc && !s.chargeless && !s.tile_valid && s.np > 0 && wants_tile_order(e, s)) return k_sort_p(e, s, true);
   return 0;
@@ -559,10 +566,8 @@ static int push_timing_hinted(Engine *e, Species &s) {
   if (timed) {
     if (!s.hp_ev[0]) for (auto &ev : s.hp_ev) VH_CHECK(hipEventCreate(&ev));
     // (read here, a cycle later: when the sort that follows is decided the host is a step ahead of this launch's end)
-    if (s.hp_pending && hipEventQuery(s.hp_ev[1]) == hipSuccess) {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, s.hp_ev[0], s.hp_ev[1]) == hipSuccess && ms > 0) s.hint_push_ms = ms;
-    }
+    const float ms = s.hp_pending ? event_ms(s.hp_ev) : -1;
+    if (ms > 0) s.pol.hint_push_ms = ms;
     s.hp_pending = false;
     VH_CHECK(hipEventRecord(s.hp_ev[0], e->stream));
   }
@@ -598,24 +603,10 @@ int vpic_hip_exchange_finish(vpic_hip_engine_t *e, const void *const *recv, int 
   ENGINE(e); if (n_recv > 0 && (!recv || !headers)) VH_FAIL("Bad message list");
   return k_exchange_finish(e, recv, n_recv, headers, flags);
 }
-// Which order a sort asked for through the ABI produces.  The reference's (by voxel, sort_p.c:48-58, with partition[])
-// unless the caller has left the choice to the engine -- vpic_hip_set_sort_order(e, 1), or vpic_hip_sort_due consulted for
-// the species (the engine's own sort policy) --: then charged species are grouped by TILE (engine.h), the order advance_p
-// is fastest on (one workgroup per tile, the tile and its halo as LDS window: push.hip).  Nothing but the array order and
-// partition[] depends on the choice.  VPIC_HIP_WINDOW=tile forces tiles (tests, experiments), =wide / =narrow the
-// reference's order and that row window.
+// Which order a sort asked for through the ABI produces (policy.h): the reference's (by voxel, sort_p.c:48-58, with partition[])
+// or TILE (engine.h), the order advance_p is fastest on.  Nothing but the array order and partition[] depends on the choice.
 static bool wants_tile_order(const Engine *e, const Species &s) {
-  if (s.np > ((int64_t)1 << 30)) return false;   // one launch: 32-bit byte offsets into the arrays
-  // (a chargeless species -- tracer copies -- is pushed without a window in any order; grouped by tile its interpolator
-  // gathers stay local, and the sort by tile only costs a quarter of the sort by voxel on a hot species: k_sort_p)
-  if (e->knobs.window == 't') return true;
-  if (e->knobs.window == 'w' || e->knobs.window == 'n') return false;
-  // a grid thinner than a tile on some axis (2-D decks: ny = 1) would give every workgroup a quarter tile or less of work;
-  // the row windows of the reference's order serve those
-  if (std::min(e->gk.nx, std::min(e->gk.ny, e->gk.nz)) < TILE_EDGE) return false;
-  // see k_advance_p: one tile held far more than its share at the last tile sort; every 32nd sort looks again
-  if (s.tile_unbalanced && (s.n_cycle & 31) != 31) return false;
-  return e->engine_order || s.adaptive;
+  return vpichip::wants_tile_order(s.pol, s.np, e->knobs.window, std::min(e->gk.nx, std::min(e->gk.ny, e->gk.nz)), e->engine_order || s.adaptive);
 }
 int vpic_hip_set_sort_order(vpic_hip_engine_t *e, int order) {
   ENGINE(e);
@@ -626,7 +617,7 @@ int vpic_hip_set_sort_order(vpic_hip_engine_t *e, int order) {
 }
 int vpic_hip_sort_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp); return k_sort_p(e, e->species[sp], wants_tile_order(e, e->species[sp])); }
 // A species that is due, sorted and pushed: the sort INSIDE the push (Species::fuse_pending) or before it, whichever took less
-// time for this species when it was last tried (engine.h, Species::sort_push_ms) -- both are timed with a pair of events that is
+// time for this species when it was last tried (policy.h: sort_inside_push) -- both are timed with a pair of events that is
 // read when the species is sorted next (the host is two steps ahead of the device at most), the loser is tried again every eighth
 // sort; sorting BEFORE the push is tried for the first time only where the launch that sorted was slow against the one before it.  between(): what the caller does between the two (hints for the push).
 static int sort_and_push(Engine *e, Species &s, bool may_fuse, const std::function<int(Species &)> &between) {
@@ -634,26 +625,11 @@ static int sort_and_push(Engine *e, Species &s, bool may_fuse, const std::functi
   may_fuse = may_fuse && e->knobs.fuse_in_step != 0;
   const bool measured = may_fuse && e->knobs.fuse_in_step < 0 && tile && s.hist_valid && !e->time_kernels;     // (a sort that has to count for itself is neither of the two)
   if (measured) {
-    if (s.sp_kind >= 0 && hipEventQuery(s.sp_ev[1]) == hipSuccess) {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, s.sp_ev[0], s.sp_ev[1]) == hipSuccess && ms > 0) s.sort_push_ms[s.sp_kind] = ms;
-      s.sp_kind = -1;
-    }
-    if (s.hp_pending && hipEventQuery(s.hp_ev[1]) == hipSuccess) {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, s.hp_ev[0], s.hp_ev[1]) == hipSuccess && ms > 0) s.hint_push_ms = ms;
-      s.hp_pending = false;
-    }
-    if (s.sp_kind < 0) {                                   // (otherwise: the last measurement has not come back -- as last time)
-      if (s.sort_push_ms[1] == 0) s.sp_last = true;        // [1] inside the push, [0] before it
-      else if (s.sort_push_ms[0] == 0)
-        // before the push for the first time: when the launch that sorted took more than 1.9 x the one that counted for it (see
-        // Species::hint_push_ms; a short run of a cold deck never pays for the experiment), or at the sixteenth sort at the latest
-        s.sp_last = !((s.hint_push_ms > 0 && s.sort_push_ms[1] > 1.9f * s.hint_push_ms) || (s.n_cycle & 15) == 15);
-      else { s.sp_last = s.sort_push_ms[1] <= s.sort_push_ms[0]; if ((s.n_cycle & 7) == 7) s.sp_last = !s.sp_last; }
-      if (e->knobs.policy_debug) fprintf(stderr, "sort and push: inside %.2f ms, before %.2f ms, the push that counted %.2f ms -> %s\n", (double)s.sort_push_ms[1], (double)s.sort_push_ms[0], (double)s.hint_push_ms, s.sp_last ? "inside" : "before");
-    }
-    may_fuse = s.sp_last;
+    const float sp_ms = s.sp_kind >= 0 ? event_ms(s.sp_ev) : -1, hp_ms = s.hp_pending ? event_ms(s.hp_ev) : -1;
+    if (sp_ms >= 0) { if (sp_ms > 0) s.pol.sort_push_ms[s.sp_kind] = sp_ms; s.sp_kind = -1; }
+    if (hp_ms >= 0) { if (hp_ms > 0) s.pol.hint_push_ms = hp_ms; s.hp_pending = false; }
+    // (while the last measurement has not come back: as last time)
+    may_fuse = s.sp_kind < 0 ? sort_inside_push(s.pol, e->knobs.policy_debug) : s.pol.sp_last;
     if (s.sp_kind < 0) {
       if (!s.sp_ev[0]) for (auto &ev : s.sp_ev) VH_CHECK(hipEventCreate(&ev));
       VH_CHECK(hipEventRecord(s.sp_ev[0], e->stream));
@@ -818,63 +794,15 @@ int vpic_hip_pack_jf(vpic_hip_engine_t *e, int dir, void *buf) { ENGINE(e); retu
 int vpic_hip_unpack_jf(vpic_hip_engine_t *e, int dir, const void *buf) { ENGINE(e); return k_unpack_face(e, dir, (const float *)buf, 1); }
 
 // src/vpic/advance.cxx:38-214 for a domain that needs no other domain
-// The adaptive decision for one species (see vpic_hip_step): reads the event pairs k_advance_p and
+// The adaptive decision for one species (see vpic_hip_step; policy.h: sort_due): reads the event pairs k_advance_p and
 // k_sort_p record while e->time_kernels is set.
 static int sort_due(Engine *e, Species &s, int max_interval, int *due) {
   e->time_kernels = true;
   s.adaptive = true;
-  float ms = 0;
-  *due = 0;
-  if (s.sort_timed && hipEventSynchronize(s.ev[3]) == hipSuccess && hipEventElapsedTime(&ms, s.ev[2], s.ev[3]) == hipSuccess) {
-    s.t_sort = ms; s.sort_timed = false;
-    const int fl = s.coarse_sorted ? 1 : 0;                // (a sort right after a change of flavour is booked to the new one: one stray sample)
-    if (s.sorted_after >= 1 && s.sorted_after <= 32) { s.s_hist[fl][s.sorted_after] = ms; s.c_hist[fl][s.sorted_after] = (ms + s.prev_sum) / s.sorted_after; }
-    // cost per step of the cycle this sort closed, booked to the flavour it ran in (cycles right after a change of
-    // flavour still carry the other one's disorder and are not counted)
-    if (s.sorted_after >= 1 && s.tile_valid && s.flavour_cycles >= 2) {
-      const int f = s.coarse_sorted ? 1 : 0;
-      const double c = (ms + s.prev_sum) / s.sorted_after;
-      s.flavour_cost[f] = s.flavour_cost[f] > 0 ? 0.5 * (s.flavour_cost[f] + c) : c;
-    }
-  }
-  if (s.push_timed && hipEventSynchronize(s.ev[1]) == hipSuccess && hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) {
-    // predicted cost of the NEXT push: the last one plus the growth to expect.  Push times grow faster than linearly
-    // once particles outrun the LDS window (a ballistic plasma leaves a tile's halo after a few steps and every deposit
-    // outside costs twelve global atomics), so the growth is the one an EARLIER cycle saw at this position when one got
-    // that far; otherwise the growth seen last (within this cycle, or -- after one push -- the first growth of the
-    // latest cycle that had two).  Every 64th cycle forgets the recorded growths, so that one that has died down gets
-    // measured again.
-    const int at = s.n_push;                            // position of the push just timed within its cycle
-    const int fl = s.coarse_sorted ? 1 : 0;
-    double *t_hist = s.t_hist[fl], *s_hist = s.s_hist[fl], *c_hist = s.c_hist[fl]; int &n_hist = s.n_hist[fl];
-    double growth = 0;
-    if (at >= 1) { growth = ms - s.t_last; if (at == 1) s.growth_first = growth; }
-    else if ((s.n_cycle & 63) != 63) growth = s.growth_first;
-    if ((s.n_cycle & 63) == 63) n_hist = 0;
-    if (at + 1 < n_hist && at + 1 < 32) growth = std::max(growth, t_hist[at + 1] - t_hist[at]);
-    if (at < 32) { t_hist[at] = ms; if (n_hist < at + 1) n_hist = at + 1; }
-    s.t_last = ms;
-    s.t_sum += ms; s.n_push++; s.push_timed = false;
-    // Sort now, after n pushes, or after one more?  Whichever has the lower cost per step, the sort included.  The sort
-    // is dearer the longer it is put off (the disorder it undoes grows: 2.4 ms after one step of a vth = 0.6 c species,
-    // 4.5 after three), so its cost is the one seen at that cycle length when there is one on record.
-    const int n = s.n_push;
-    const double t_next = (double)ms + (growth > 0 ? growth : 0);
-    const double sort_now = (n <= 32 && s_hist[n] > 0) ? s_hist[n] : s.t_sort;
-    double sort_later = (n + 1 <= 32 && s_hist[n + 1] > 0) ? s_hist[n + 1] : sort_now;
-    if (sort_later < sort_now) sort_later = sort_now;
-    if ((s.n_cycle & 63) == 63) sort_later = sort_now;
-    *due = (sort_later + s.t_sum + t_next) * n >= (sort_now + s.t_sum) * (n + 1);
-    // What whole cycles of n and of n + 1 pushes actually cost per step, when both are on record, overrules the
-    // prediction; and every eighth cycle is ended one push earlier than the last one when no cycle of that length is on record yet (the
-    // prediction cannot know what a sort costs after fewer steps than it has ever been put off).
-    if ((s.n_cycle & 63) == 63) for (int k = 0; k < 34; k++) c_hist[k] = 0;
-    if (n <= 32 && c_hist[n] > 0 && c_hist[n + 1] > 0) *due = c_hist[n] <= c_hist[n + 1];
-    else if (!*due && n <= 32 && c_hist[n] == 0 && (s.n_cycle & 7) == 7 && n == s.sorted_after - 1) *due = 1;   // one push earlier than last time
-    if (e->knobs.policy_debug) fprintf(stderr, "sort policy: n=%d T=%.3f T_next=%.3f S_now=%.3f S_later=%.3f sum=%.3f c[n]=%.3f c[n+1]=%.3f flavour %d (%.3f / %.3f per step) -> %s\n", n, (double)ms, t_next, sort_now, sort_later, s.t_sum, n <= 32 ? c_hist[n] : 0.0, n <= 32 ? c_hist[n + 1] : 0.0, (int)s.coarse_sorted, s.flavour_cost[0], s.flavour_cost[1], *due ? "sort" : "go on");
-
-  }
-  if (!s.sorted_once || (max_interval > 0 && s.n_push >= max_interval)) *due = 1;
+  const float sort_ms = s.sort_timed ? event_ms(s.ev + 2, true) : -1, push_ms = s.push_timed ? event_ms(s.ev, true) : -1;
+  if (sort_ms >= 0) s.sort_timed = false;
+  if (push_ms >= 0) s.push_timed = false;
+  *due = vpichip::sort_due(s.pol, sort_ms, push_ms, s.coarse_sorted, s.tile_valid, max_interval, e->knobs.policy_debug);
   return 0;
 }
 int vpic_hip_sort_due(vpic_hip_engine_t *e, int sp, int max_interval, int *due) {
@@ -892,8 +820,8 @@ int vpic_hip_species_sort_hint(vpic_hip_engine_t *e, int sp) {
 int vpic_hip_species_stats(vpic_hip_engine_t *e, int sp, int64_t out[8]) {
   ENGINE(e); SPECIES(e, sp); if (!out) VH_FAIL("Bad output");
   const Species &s = e->species[sp];
-  out[0] = s.crossed_host ? s.crossed_host[0] : 0; out[1] = s.crossed_host ? s.crossed_host[1] : 0; out[2] = s.crossed_host ? s.crossed_host[3] : 0;
-  out[3] = s.n_cycle; out[4] = s.early_sorts; out[5] = s.tile_unbalanced; out[6] = s.coarse_sorted; out[7] = s.n_holes;
+  out[0] = s.crossed_host ? s.crossed_host[PW_CROSSERS] : 0; out[1] = s.crossed_host ? s.crossed_host[PW_FULLEST_TILE] : 0; out[2] = s.crossed_host ? s.crossed_host[PW_MISSED] : 0;
+  out[3] = s.pol.n_cycle; out[4] = s.pol.early_sorts; out[5] = s.pol.tile_unbalanced; out[6] = s.coarse_sorted; out[7] = s.n_holes;
   return 0;
 }
 int vpic_hip_species_sort_order(vpic_hip_engine_t *e, int sp, int *order) {
@@ -931,23 +859,9 @@ int vpic_hip_step(vpic_hip_engine_t *e, int64_t step, int sort_interval) {
     Species &s = e->species[k];
     int due = sort_interval > 0 && step % sort_interval == 0;
     if (sort_interval < 0 && sort_due(e, s, -sort_interval, &due)) return 1;
-    // A fixed interval that outlasts the windows: once the species' particles have left what their tiles' windows can follow
-    // (three cells: ~27 steps of the two-stream beams), every deposit is twelve global atomics and a launch costs four times
-    // what it should (round 3: sort_interval = 40 ran at 14 G pushes/s).  The runs that missed the windows in the last launch
-    // (a pinned word the device publishes behind every launch: stale by a launch or two, which is early enough) cost ~0.17 ns
-    // and more each (they pile up on the same few accumulators: round 3 measured +50 ms per launch), a sort ~18 ps per particle:
-    // when one launch missed more than 32 runs per tile -- half of where the windows stop following (publish_counter_kernel) --
-    // and at least two steps are left, sort now.
-    if (!due && sort_interval > 0 && e->knobs.early_sort && s.tile_valid && !s.chargeless && s.crossed_host) {
-      const int64_t left = sort_interval - step % sort_interval;
-      // (word 4: the sort cycle the count was taken in -- the host runs ahead of the device, and a count from before the last sort must not trigger another)
-      // ... and the steps left must pay for it: a missed run costs ~0.34 ns (39.3 against 34.1 ms per step at 7.4e6 of them per
-      // launch, profiles/r04_sort_interval_40_step_by_step.txt), an unscheduled sort ~19 ps per particle (it cannot happen inside
-      // the push), and the misses grow: sort when misses x steps left exceed a 27th of the particles.  (The heated two-stream
-      // deck at interval 10 reaches 32 runs per tile three steps before its scheduled sort: not worth one of its own.)
-      const int64_t missed = s.crossed_host[3];
-      if (s.crossed_host[4] == (unsigned)s.n_cycle && left >= 2 && missed > 32ll * make_tile_k(e->gk).ntiles && missed * left * 27 > s.np) { due = 1; s.early_sorts++; }
-    }
+    // a fixed interval that outlasts the windows (policy.h: early_sort)
+    if (!due && sort_interval > 0 && e->knobs.early_sort && s.tile_valid && !s.chargeless && s.crossed_host &&
+        early_sort(s.pol, s.crossed_host[PW_MISSED], s.crossed_host[PW_CYCLE], sort_interval - step % sort_interval, make_tile_k(e->gk).ntiles, s.np)) due = 1;
     if (due) due_list.push_back((int)k);
   }
   std::vector<char> pushed(e->species.size(), 0), sort_first(e->species.size(), 0);

@@ -522,37 +522,17 @@ __global__ void publish_word_kernel(unsigned *__restrict__ host_word, const unsi
 
 int k_sort_p(Engine *e, Species &s, bool tile_order, bool may_fuse) {
   const TileK tk = make_tile_k(e->gk);
-  // by tile only: species most of whose particles change cell every step (push.hip keeps the fraction); VPIC_HIP_TILE_COARSE=0|1 overrides
-  // (measured, 128^3 x 32 ppc two-stream with adaptive sorting: vth = 0.6 c 7.6 -> 5.8 ms per step, 0.24 c 5.8 -> 4.8, 0.1 c
-  // even, cold beams 3 % slower by tile only: the switch is at a fifth of the particles crossing per step)
-  // Which of the two is a matter of sizes too (3 M particles per species at 50 ppc, the production deck at test size: by
-  // tile only is 20 % SLOWER), so where the engine's sort policy times the cycles it is decided by measurement: the
-  // other flavour is tried for a few cycles now and then, the cheaper one per step is kept (sort_due records the costs).
-  // Without timings: by tile only from a fifth of the particles crossing per step.
-  if (tile_order) {
-    // (a species of a few million particles does not fill the GPU with 2048-particle workgroups: there the count's serial
-    // LDS chains and the unordered push are slower -- not even tried below 8 M)
-    const bool eligible = s.np >= ((int64_t)8 << 20) && (s.cross_frac > 0.20 || (s.coarse_order && s.cross_frac > 0.15));
-    if (!eligible) { s.coarse_order = false; s.flavour_cost[0] = s.flavour_cost[1] = 0; s.flavour_cycles = 0; }
-    else if (!s.adaptive) s.coarse_order = true;
-    else {
-      const int cur = s.coarse_order ? 1 : 0, other = 1 - cur;
-      bool change = false;
-      if ((s.n_cycle & 127) == 127) s.flavour_cost[other] = 0;                       // look again now and then
-      if (s.flavour_cycles >= 4 && s.flavour_cost[cur] > 0) {
-        if (s.flavour_cost[other] == 0) change = true;                                // never tried (or forgotten): try it
-        else if (s.flavour_cost[other] < 0.97 * s.flavour_cost[cur]) change = true;   // on record and cheaper
-      }
-      if (change) {
-        s.coarse_order = !s.coarse_order; s.flavour_cycles = 0;
-      }
-    }
-  }
-  bool coarse = tile_order && (s.coarse_order || s.chargeless);   // (nothing to deposit: no runs of equal cells to keep together)
-  if (tile_order && e->knobs.tile_coarse >= 0) coarse = e->knobs.tile_coarse != 0;
+  const int n1 = (tile_order ? tk.ntiles * TILE_CELLS : e->gk.nv) + 1;
+  // by tile only or by cell within a tile, inside the push that follows, which count (policy.h: plan_sort)
+  SortInputs in;
+  in.tile_order = tile_order; in.may_fuse = may_fuse; in.np = s.np; in.n_sorted = s.n_sorted;
+  in.adaptive = s.adaptive; in.chargeless = s.chargeless; in.has_tags = s.has_tags;
+  in.tile_valid = s.tile_valid; in.coarse_sorted = s.coarse_sorted; in.counts_ready = s.hist_valid && s.hist && s.hist_count >= n1;
+  in.det_acc = e->det_acc; in.time_kernels = e->time_kernels; in.tile_coarse = e->knobs.tile_coarse; in.old_sort = e->knobs.old_sort;
+  const SortPlan pl = plan_sort(s.pol, in);
+  const bool coarse = pl.coarse;
   const int nv = e->gk.nv;
-  // keys: voxels (the reference's order; partition[] as sort_p.c:32 leaves it), or tile-major (see engine.h)
-  const int n1 = (tile_order ? tk.ntiles * TILE_CELLS : nv) + 1;
+  // keys: voxels (the reference's order; partition[] as sort_p.c:32 leaves it), or tile-major (see engine.h): n1 - 1 of them
   if (!s.partition) VH_CHECK(hipMalloc(&s.partition, sizeof(int) * (nv + 1)));       // sort_p.c:32
   if (tile_order && s.tpart_count < n1) {
     if (s.tpart) VH_CHECK(hipFree(s.tpart));
@@ -560,7 +540,6 @@ int k_sort_p(Engine *e, Species &s, bool tile_order, bool may_fuse) {
     VH_CHECK(hipMalloc(&s.tpart, sizeof(int) * n1));
     s.tpart_count = n1;
   }
-  const bool was_tile_valid = s.tile_valid;
   s.tile_valid = false;
   if (s.np == s.n_holes) { s.np = 0; s.n_holes = 0; }                         // nothing alive
   if (s.np == 0) return 0;                                                     // sort_p.c:35
@@ -570,12 +549,9 @@ int k_sort_p(Engine *e, Species &s, bool tile_order, bool may_fuse) {
     VH_CHECK(hipMalloc(&s.tag2_aux, sizeof(int64_t) * s.max_np));
   }
   const int np = (int)s.np;
-  // The sort inside the push (Species::fuse_pending): by tile and cell, counted by the push before, the species as that push
-  // left it, and the caller pushes it next -- then nothing moves here.  (Not for: tags, which ride outside the push; the
-  // deterministic mode and the phased push, which run other instances; the adaptive policy, which times sort and push apart.)
+  // the sort inside the push (Species::fuse_pending)
   s.fuse_pending = false;
-  if (may_fuse && tile_order && !coarse && was_tile_valid && !s.coarse_sorted && !s.tile_unbalanced && s.hist_valid && s.hist && s.hist_count >= n1 &&
-      !s.has_tags && !e->det_acc && !e->time_kernels && !e->knobs.old_sort && s.np <= ((int64_t)1 << 30) && s.np == s.n_sorted) {
+  if (pl.fuse) {
     if (s.tpart2_count < n1) {
       if (s.tpart2) VH_CHECK(hipFree(s.tpart2));
       s.tpart2 = nullptr; s.tpart2_count = 0;
@@ -585,15 +561,10 @@ int k_sort_p(Engine *e, Species &s, bool tile_order, bool may_fuse) {
     s.fuse_pending = true; s.tile_valid = true;         // (the array is as it was: the push that follows sorts it)
     return 0;
   }
-  // Which count / scatter: a workgroup at a time (LDS table of up to 512 distinct keys per 2048 particles), or -- for a hot
-  // species in the reference's order, where a chunk's particles sit in nearly as many voxels as there are particles and
-  // the count's table would overflow into one global atomic per particle -- the COUNT a wavefront at a time (measured, 67 M
-  // particles at vth = 0.6 c by voxel: count 2.4 ms against 1.8; the scatter stays by workgroup there, 2.7 ms against 7.3)
-  const bool by_wave = e->knobs.old_sort, count_by_wave = by_wave || (!tile_order && s.cross_frac > 0.15);
+  const bool by_wave = pl.by_wave, count_by_wave = pl.count_by_wave;
   int *starts = tile_order ? s.tpart : s.partition;
   if (e->time_kernels) { if (!s.ev[0]) for (int i = 0; i < 4; i++) VH_CHECK(hipEventCreate(&s.ev[i])); (void)hipEventRecord(s.ev[2], e->stream); }
-  // the push before this sort may have counted already (Species::hist, push.hip): then the sort starts at its scan
-  const bool counted = tile_order && !coarse && s.hist_valid && s.hist && s.hist_count >= n1;
+  const bool counted = pl.counted;
   const int *counts = counted ? s.hist : e->sort_next;
   s.hist_valid = false;
   if (counted) {}
@@ -640,7 +611,7 @@ int k_sort_finish(Engine *e, Species &s, bool tile_order, bool coarse) {
     unsigned *word = reinterpret_cast<unsigned *>(e->counters + 200);      // (scratch word of the counter block; the maximum reaches the host's mapped word by a plain store)
     hipLaunchKernelGGL(clear_word_kernel, dim3(1), dim3(1), 0, e->stream, word);
     hipLaunchKernelGGL(tile_max_kernel, dim3((unsigned)std::min(256, (tk.ntiles + 255) / 256)), dim3(256), 0, e->stream, s.tpart, tk.ntiles, word);
-    hipLaunchKernelGGL(publish_word_kernel, dim3(1), dim3(1), 0, e->stream, s.crossed_host_dev + 1, (const unsigned *)word);
+    hipLaunchKernelGGL(publish_word_kernel, dim3(1), dim3(1), 0, e->stream, s.crossed_host_dev + PW_FULLEST_TILE, (const unsigned *)word);
   }
   VH_CHECK(hipGetLastError());
   std::swap(s.p, s.aux);
@@ -648,11 +619,9 @@ int k_sort_finish(Engine *e, Species &s, bool tile_order, bool coarse) {
   s.np -= s.n_holes; s.n_holes = 0;                     // the dead slots were not copied
   s.partition_valid = !tile_order;
   s.tile_valid = tile_order; s.n_sorted = s.np; s.coarse_sorted = coarse;
-  if (tile_order) s.tile_unbalanced = false;          // the push looks at the fullest tile of THIS sort
   if (s.crossed_dev) VH_CHECK(hipMemsetAsync(s.crossed_dev + 2, 0, sizeof(unsigned), e->stream));   // the windows sit on their tiles again (PushParams::follow)
   if (e->time_kernels) { (void)hipEventRecord(s.ev[3], e->stream); s.sort_timed = true; }
-  s.sorted_once = true; s.sorted_after = s.n_push; s.prev_sum = s.t_sum; s.t_sum = 0; s.n_push = 0; s.n_cycle++;
-  if (tile_order) s.flavour_cycles++;
+  s.pol.new_cycle(tile_order);
   return 0;
 }
 

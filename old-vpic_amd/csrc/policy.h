@@ -1,0 +1,284 @@
+// policy.h -- the engine's sort and push decisions (vpic_hip_step, sort_p, advance_p) over plain values: the callers read
+// their HIP events and pinned words once and hand in what they read.  Plain C++17, no HIP: tests/policy_check.cpp builds it
+// with the host compiler alone.
+#pragma once
+#include <stdint.h>
+#include <stdio.h>
+#include <algorithm>
+
+namespace vpichip {
+
+constexpr int TILE_EDGE = 4;   // cells per edge of a tile (TILE order, engine.h)
+
+// the words a species' kernels publish behind their launches into mapped pinned memory (Species::crossed_host): crossers of
+// the last push, particles of the fullest tile at the last tile sort, cursors of the last sort that did not end where the next
+// key begins (Species::fuse_pending), runs that missed the tile windows in the last push, the sort cycle that push belonged to
+enum PinnedWord { PW_CROSSERS = 0, PW_FULLEST_TILE, PW_SORT_CHECK, PW_MISSED, PW_CYCLE };
+
+// What the decisions about one species remember (Species::pol).
+struct Policy {
+  // adaptive sorting (vpic_hip_step, sort_interval < 0; see sort_due): cost of a sort, and sum / number of the push times
+  // since the last sort (ms)
+  bool sorted_once = false;
+  double t_sort = 0, t_sum = 0; int n_push = 0;
+  double t_last = 0, growth_first = 0; int n_cycle = 0;   // n_cycle: sorts so far
+  // (one set per sort flavour, see flavour_cost: [0] by cell within a tile or by voxel, [1] by tile only)
+  double t_hist[2][32] = {{0}}; int n_hist[2] = {0, 0};                // ... the push times of earlier cycles by position in the cycle
+  double s_hist[2][33] = {{0}}; int sorted_after = 0;          // ... what a sort cost after n pushes (more steps, more disorder), pushes before the last sort
+  double c_hist[2][34] = {{0}}; double prev_sum = 0;           // ... measured cost per step (sort included) of whole cycles of n pushes; push time of the last whole cycle
+  bool coarse_order = false;      // tile sorts group this species by tile only (particles.hip)
+  // ... chosen by measurement when the engine's sort policy times the cycles: cost per step of whole cycles in either
+  // flavour ([0] by cell within a tile, [1] by tile only; 0 = not on record), cycles since the flavour last changed
+  double flavour_cost[2] = {0, 0}; int flavour_cycles = 0;
+  // ... inside the push or before it: decided by MEASUREMENT (engine.hip: sort_and_push).  A species whose cells move as one (cold
+  // beams) lands in its new order in long runs and the sorting launch beats sort + push (29.7 ms against 20 + 16.8 at 256^3 x
+  // 64 ppc); one whose particles have spread (the same deck from step ~120 on) writes runs of two and loses (60 against 20 +
+  // 18.5).  ms of this species' sort + push in either way (0: not on record), the choice made last
+  float sort_push_ms[2] = {0, 0}; bool sp_last = true;
+  // ... and of the push that counted for the sort (the last, slowest plain launch of the cycle): the yardstick that says whether
+  // sorting before the push is worth a first try -- 20 + 17 ms against 27-30 inside the push where the counting launch took
+  // 17.6 (ratio 1.6: no), 20 + 18.5 against 60 where it took 24 (2.5: yes)
+  float hint_push_ms = 0;
+  bool wide_window = false;       // advance_p instance with the double-precision LDS window (crossing-heavy species; push.hip)
+  bool tile_unbalanced = false;   // the fullest tile alone would keep its workgroup busy several times longer than a balanced launch takes
+  double cross_frac = 0;          // fraction of the particles that left their cell in the last advance_p (one launch behind)
+  int64_t np_pushed_last = 0;     // particles of the previous advance_p launch (denominator of the crossing fraction)
+  int64_t early_sorts = 0;        // sorts vpic_hip_step made ahead of a fixed interval because the deposits had begun to miss the windows
+
+  // a sort has finished (k_sort_finish): a new cycle begins
+  void new_cycle(bool tile_order) {
+    if (tile_order) tile_unbalanced = false;          // the push looks at the fullest tile of THIS sort
+    sorted_once = true; sorted_after = n_push; prev_sum = t_sum; t_sum = 0; n_push = 0; n_cycle++;
+    if (tile_order) flavour_cycles++;
+  }
+};
+
+// The adaptive decision for one species (vpic_hip_step, vpic_hip_sort_due): books the times of the last sort and push
+// (sort_ms, push_ms: < 0 when not timed since) and says whether to sort before the next push.
+inline bool sort_due(Policy &s, double sort_ms, double push_ms, bool coarse_sorted, bool tile_valid, int max_interval, bool debug) {
+  bool due = false;
+  if (const double ms = sort_ms; ms >= 0) {
+    s.t_sort = ms;
+    const int fl = coarse_sorted ? 1 : 0;                  // (a sort right after a change of flavour is booked to the new one: one stray sample)
+    if (s.sorted_after >= 1 && s.sorted_after <= 32) { s.s_hist[fl][s.sorted_after] = ms; s.c_hist[fl][s.sorted_after] = (ms + s.prev_sum) / s.sorted_after; }
+    // cost per step of the cycle this sort closed, booked to the flavour it ran in (cycles right after a change of
+    // flavour still carry the other one's disorder and are not counted)
+    if (s.sorted_after >= 1 && tile_valid && s.flavour_cycles >= 2) {
+      const int f = coarse_sorted ? 1 : 0;
+      const double c = (ms + s.prev_sum) / s.sorted_after;
+      s.flavour_cost[f] = s.flavour_cost[f] > 0 ? 0.5 * (s.flavour_cost[f] + c) : c;
+    }
+  }
+  if (const double ms = push_ms; ms >= 0) {
+    // predicted cost of the NEXT push: the last one plus the growth to expect.  Push times grow faster than linearly
+    // once particles outrun the LDS window (a ballistic plasma leaves a tile's halo after a few steps and every deposit
+    // outside costs twelve global atomics), so the growth is the one an EARLIER cycle saw at this position when one got
+    // that far; otherwise the growth seen last (within this cycle, or -- after one push -- the first growth of the
+    // latest cycle that had two).  Every 64th cycle forgets the recorded growths, so that one that has died down gets
+    // measured again.
+    const int at = s.n_push;                            // position of the push just timed within its cycle
+    const int fl = coarse_sorted ? 1 : 0;
+    double *t_hist = s.t_hist[fl], *s_hist = s.s_hist[fl], *c_hist = s.c_hist[fl]; int &n_hist = s.n_hist[fl];
+    double growth = 0;
+    if (at >= 1) { growth = ms - s.t_last; if (at == 1) s.growth_first = growth; }
+    else if ((s.n_cycle & 63) != 63) growth = s.growth_first;
+    if ((s.n_cycle & 63) == 63) n_hist = 0;
+    if (at + 1 < n_hist && at + 1 < 32) growth = std::max(growth, t_hist[at + 1] - t_hist[at]);
+    if (at < 32) { t_hist[at] = ms; if (n_hist < at + 1) n_hist = at + 1; }
+    s.t_last = ms;
+    s.t_sum += ms; s.n_push++;
+    // Sort now, after n pushes, or after one more?  Whichever has the lower cost per step, the sort included.  The sort
+    // is dearer the longer it is put off (the disorder it undoes grows: 2.4 ms after one step of a vth = 0.6 c species,
+    // 4.5 after three), so its cost is the one seen at that cycle length when there is one on record.
+    const int n = s.n_push;
+    const double t_next = ms + (growth > 0 ? growth : 0);
+    const double sort_now = (n <= 32 && s_hist[n] > 0) ? s_hist[n] : s.t_sort;
+    double sort_later = (n + 1 <= 32 && s_hist[n + 1] > 0) ? s_hist[n + 1] : sort_now;
+    if (sort_later < sort_now) sort_later = sort_now;
+    if ((s.n_cycle & 63) == 63) sort_later = sort_now;
+    due = (sort_later + s.t_sum + t_next) * n >= (sort_now + s.t_sum) * (n + 1);
+    // What whole cycles of n and of n + 1 pushes actually cost per step, when both are on record, overrules the
+    // prediction; and every eighth cycle is ended one push earlier than the last one when no cycle of that length is on record yet (the
+    // prediction cannot know what a sort costs after fewer steps than it has ever been put off).
+    if ((s.n_cycle & 63) == 63) for (int k = 0; k < 34; k++) c_hist[k] = 0;
+    if (n <= 32 && c_hist[n] > 0 && c_hist[n + 1] > 0) due = c_hist[n] <= c_hist[n + 1];
+    else if (!due && n <= 32 && c_hist[n] == 0 && (s.n_cycle & 7) == 7 && n == s.sorted_after - 1) due = true;   // one push earlier than last time
+    if (debug) fprintf(stderr, "sort policy: n=%d T=%.3f T_next=%.3f S_now=%.3f S_later=%.3f sum=%.3f c[n]=%.3f c[n+1]=%.3f flavour %d (%.3f / %.3f per step) -> %s\n", n, ms, t_next, sort_now, sort_later, s.t_sum, n <= 32 ? c_hist[n] : 0.0, n <= 32 ? c_hist[n + 1] : 0.0, (int)coarse_sorted, s.flavour_cost[0], s.flavour_cost[1], due ? "sort" : "go on");
+  }
+  if (!s.sorted_once || (max_interval > 0 && s.n_push >= max_interval)) due = true;
+  return due;
+}
+
+// Which order a sort asked for through the ABI produces: TILE (true) or the reference's by voxel.  engine_choice: the caller
+// has left the choice to the engine (vpic_hip_set_sort_order(e, 1), or the engine's own sort policy consulted); window: the
+// VPIC_HIP_WINDOW knob; min_axis: the fewest cells of the grid along an axis.
+inline bool wants_tile_order(const Policy &s, int64_t np, int window, int min_axis, bool engine_choice) {
+  if (np > ((int64_t)1 << 30)) return false;   // one launch: 32-bit byte offsets into the arrays
+  // (a chargeless species -- tracer copies -- is pushed without a window in any order; grouped by tile its interpolator
+  // gathers stay local, and the sort by tile only costs a quarter of the sort by voxel on a hot species: k_sort_p)
+  if (window == 't') return true;
+  if (window == 'w' || window == 'n') return false;
+  // a grid thinner than a tile on some axis (2-D decks: ny = 1) would give every workgroup a quarter tile or less of work;
+  // the row windows of the reference's order serve those
+  if (min_axis < TILE_EDGE) return false;
+  // see plan_push: one tile held far more than its share at the last tile sort; every 32nd sort looks again
+  if (s.tile_unbalanced && (s.n_cycle & 31) != 31) return false;
+  return engine_choice;
+}
+
+// A species that is due, sorted and pushed: the sort INSIDE the push (true) or before it, whichever took less time for this
+// species when it was last tried (sort_push_ms, read by the caller); the loser is tried again every eighth sort.
+inline bool sort_inside_push(Policy &s, bool debug) {
+  if (s.sort_push_ms[1] == 0) s.sp_last = true;        // [1] inside the push, [0] before it
+  else if (s.sort_push_ms[0] == 0)
+    // before the push for the first time: when the launch that sorted took more than 1.9 x the one that counted for it (see
+    // Policy::hint_push_ms; a short run of a cold deck never pays for the experiment), or at the sixteenth sort at the latest
+    s.sp_last = !((s.hint_push_ms > 0 && s.sort_push_ms[1] > 1.9f * s.hint_push_ms) || (s.n_cycle & 15) == 15);
+  else { s.sp_last = s.sort_push_ms[1] <= s.sort_push_ms[0]; if ((s.n_cycle & 7) == 7) s.sp_last = !s.sp_last; }
+  if (debug) fprintf(stderr, "sort and push: inside %.2f ms, before %.2f ms, the push that counted %.2f ms -> %s\n", (double)s.sort_push_ms[1], (double)s.sort_push_ms[0], (double)s.hint_push_ms, s.sp_last ? "inside" : "before");
+  return s.sp_last;
+}
+
+// A fixed interval that outlasts the windows: once the species' particles have left what their tiles' windows can follow
+// (three cells: ~27 steps of the two-stream beams), every deposit is twelve global atomics and a launch costs four times
+// what it should (round 3: sort_interval = 40 ran at 14 G pushes/s).  The runs that missed the windows in the last launch
+// (PW_MISSED: stale by a launch or two, which is early enough) cost ~0.17 ns and more each (they pile up on the same few
+// accumulators: round 3 measured +50 ms per launch), a sort ~18 ps per particle: when one launch missed more than 32 runs per
+// tile -- half of where the windows stop following (publish_counter_kernel) -- and at least two steps are left, sort now.
+// (cycle, PW_CYCLE: the sort cycle the count was taken in -- the host runs ahead of the device, and a count from before the
+// last sort must not trigger another)
+inline bool early_sort(Policy &s, int64_t missed, unsigned cycle, int64_t left, int64_t ntiles, int64_t np) {
+  // ... and the steps left must pay for it: a missed run costs ~0.34 ns (39.3 against 34.1 ms per step at 7.4e6 of them per
+  // launch, profiles/r04_sort_interval_40_step_by_step.txt), an unscheduled sort ~19 ps per particle (it cannot happen inside
+  // the push), and the misses grow: sort when misses x steps left exceed a 27th of the particles.  (The heated two-stream
+  // deck at interval 10 reaches 32 runs per tile three steps before its scheduled sort: not worth one of its own.)
+  if (cycle == (unsigned)s.n_cycle && left >= 2 && missed > 32ll * ntiles && missed * left * 27 > np) { s.early_sorts++; return true; }
+  return false;
+}
+
+// k_sort_p: what the sort of a species asked for (tile_order; may_fuse: the caller pushes it next) is, and which count it takes.
+// counts_ready: the push before counted for this sort (Species::hist_valid, big enough); tile_coarse, old_sort: knobs
+struct SortInputs {
+  bool tile_order = false, may_fuse = false, adaptive = false, chargeless = false, has_tags = false, tile_valid = false, coarse_sorted = false;
+  bool counts_ready = false, det_acc = false, time_kernels = false, old_sort = false; int tile_coarse = -1; int64_t np = 0, n_sorted = 0;
+};
+// coarse: by tile only; fuse: inside the push that follows (nothing moves now); counted: from the push's counts; by_wave, count_by_wave: the
+// scatter and count a wavefront at a time
+struct SortPlan { bool coarse = false, fuse = false, counted = false, by_wave = false, count_by_wave = false; };
+inline SortPlan plan_sort(Policy &s, const SortInputs &in) {
+  SortPlan pl;
+  // by tile only: species most of whose particles change cell every step (the push keeps the fraction); VPIC_HIP_TILE_COARSE=0|1 overrides
+  // (measured, 128^3 x 32 ppc two-stream with adaptive sorting: vth = 0.6 c 7.6 -> 5.8 ms per step, 0.24 c 5.8 -> 4.8, 0.1 c
+  // even, cold beams 3 % slower by tile only: the switch is at a fifth of the particles crossing per step)
+  // Which of the two is a matter of sizes too (3 M particles per species at 50 ppc, the production deck at test size: by
+  // tile only is 20 % SLOWER), so where the engine's sort policy times the cycles it is decided by measurement: the
+  // other flavour is tried for a few cycles now and then, the cheaper one per step is kept (sort_due records the costs).
+  // Without timings: by tile only from a fifth of the particles crossing per step.
+  if (in.tile_order) {
+    // (a species of a few million particles does not fill the GPU with 2048-particle workgroups: there the count's serial
+    // LDS chains and the unordered push are slower -- not even tried below 8 M)
+    const bool eligible = in.np >= ((int64_t)8 << 20) && (s.cross_frac > 0.20 || (s.coarse_order && s.cross_frac > 0.15));
+    if (!eligible) { s.coarse_order = false; s.flavour_cost[0] = s.flavour_cost[1] = 0; s.flavour_cycles = 0; }
+    else if (!in.adaptive) s.coarse_order = true;
+    else {
+      const int cur = s.coarse_order ? 1 : 0, other = 1 - cur;
+      bool change = false;
+      if ((s.n_cycle & 127) == 127) s.flavour_cost[other] = 0;                       // look again now and then
+      if (s.flavour_cycles >= 4 && s.flavour_cost[cur] > 0) {
+        if (s.flavour_cost[other] == 0) change = true;                                // never tried (or forgotten): try it
+        else if (s.flavour_cost[other] < 0.97 * s.flavour_cost[cur]) change = true;   // on record and cheaper
+      }
+      if (change) {
+        s.coarse_order = !s.coarse_order; s.flavour_cycles = 0;
+      }
+    }
+  }
+  pl.coarse = in.tile_order && (s.coarse_order || in.chargeless);   // (nothing to deposit: no runs of equal cells to keep together)
+  if (in.tile_order && in.tile_coarse >= 0) pl.coarse = in.tile_coarse != 0;
+  // The sort inside the push: by tile and cell, counted by the push before, the species as that push left it, and the caller
+  // pushes it next -- then nothing moves here.  (Not for: tags, which ride outside the push; the deterministic mode and the
+  // phased push, which run other instances; the adaptive policy, which times sort and push apart.)
+  pl.fuse = in.may_fuse && in.tile_order && !pl.coarse && in.tile_valid && !in.coarse_sorted && !s.tile_unbalanced && in.counts_ready &&
+            !in.has_tags && !in.det_acc && !in.time_kernels && !in.old_sort && in.np <= ((int64_t)1 << 30) && in.np == in.n_sorted;
+  // Which count / scatter: a workgroup at a time (LDS table of up to 512 distinct keys per 2048 particles), or -- for a hot
+  // species in the reference's order, where a chunk's particles sit in nearly as many voxels as there are particles and
+  // the count's table would overflow into one global atomic per particle -- the COUNT a wavefront at a time (measured, 67 M
+  // particles at vth = 0.6 c by voxel: count 2.4 ms against 1.8; the scatter stays by workgroup there, 2.7 ms against 7.3)
+  pl.by_wave = in.old_sort;
+  pl.count_by_wave = pl.by_wave || (!in.tile_order && s.cross_frac > 0.15);
+  // the push before this sort may have counted already (Species::hist, push.hip): then the sort starts at its scan
+  pl.counted = in.tile_order && !pl.coarse && in.counts_ready;
+  return pl;
+}
+
+// k_advance_p: which advance_p_kernel instance a push launches, and with what
+struct PushInputs {
+  int phase = 0;                               // vpic_hip_advance_p_phase: 0 the whole species, 1 / 2 its boundary / interior tiles
+  int64_t np = 0, n_sorted = 0; double ppc = 0;
+  unsigned crossers = 0, fullest_tile = 0;     // the pinned words PW_CROSSERS, PW_FULLEST_TILE
+  int window = 0, iters = 0, stage = -1; int64_t tail_sort_min = 0; bool no_tail_sort = false;   // knobs
+  int wx[2] = {0, 0}, wmargin = 0, threads = 0, max_iters = 0;   // row windows' cells (narrow, wide), margin, workgroup, most passes
+  bool tile_valid = false, chargeless = false, coarse_sorted = false, det_acc = false, time_kernels = false;
+  bool fuse_pending = false, hist_request = false, hist_valid = false, fuse_buffers = false;   // fuse_buffers: second buffer and tpart2 allocated
+};
+enum class PushInstance { chargeless, det_tile_only, det_tile, det_row, tile_only, tile_sort, tile_hist, tile, row_wide, row_narrow };
+// tiled: one workgroup per tile; fuse: the sort inside this push; sort_first: one was pending and cannot be (sort the ordinary
+// way, then push); regroup_tail: the appended particles by tile first (k_tail_sort); hist: count for the next sort; det: deterministic
+struct PushPlan {
+  bool tiled = false, fuse = false, sort_first = false, regroup_tail = false, hist = false, det = false; int stage = 0;
+  PushInstance instance = PushInstance::row_narrow;
+};
+
+// Which row window, and passes per wavefront: a workgroup's chunk should span a little less than the LDS window (measured,
+// tools/iters_sweep.sh: 32 ppc best at 6 passes, 64 ppc at 12, 512 ppc at 64; one pass too many and the chunk overflows the window)
+inline int push_passes(Policy &s, const PushInputs &in) {
+  // Which window: the crossing fraction of this species' previous launch (a pinned word the device wrote behind
+  // that launch; a stale value only delays the switch) with hysteresis; VPIC_HIP_WINDOW=wide|narrow overrides.
+  if (in.phase != 2) {
+    const double frac = s.np_pushed_last > 0 ? (double)in.crossers / (double)s.np_pushed_last : 0.0;
+    s.cross_frac = frac;
+    if (frac > 0.30) s.wide_window = true; else if (frac < 0.20) s.wide_window = false;
+    if (in.window == 'w') s.wide_window = true; else if (in.window == 'n') s.wide_window = false;
+    s.np_pushed_last = in.np;
+  }
+  const int wx = in.wx[s.wide_window ? 1 : 0];
+  const int it = (int)(0.9 * (wx - 2 * in.wmargin) * in.ppc / in.threads);
+  if (in.iters > 0) return in.iters;   // tuning experiments
+  return it < 1 ? 1 : it > in.max_iters ? in.max_iters : it;
+}
+
+// the rest, once push_passes' passes have split the species into n_seg launches
+inline PushPlan plan_push(Policy &s, const PushInputs &in, int n_seg) {
+  PushPlan pl;
+  // A tile is one workgroup's work.  When the fullest tile alone would take several times what the whole launch takes
+  // if balanced (1280 workgroups run at a time: 256 CUs x 5), the species is too clumped for tiles: this launch falls
+  // back to the row windows and the next sort to the reference's order.  (The count is the last tile sort's, read from
+  // pinned memory without waiting: a stale value only delays the switch.)
+  // (phase 2 keeps what phase 1 decided: the word is written by the sort's kernels while the host runs ahead of them, and a
+  // flip between the two launches of one push would leave the interior tiles unpushed with the boundary movers on the wire)
+  if (in.phase != 2 && in.tile_valid && (double)in.fullest_tile * 1280.0 > 4.0 * (double)in.np && in.fullest_tile > 65536u) s.tile_unbalanced = true;
+  pl.tiled = in.phase == 2 ? true : (in.tile_valid && !s.tile_unbalanced && !in.chargeless && n_seg == 1);   // (phase 2 only runs behind a phase 1 that split the tiles: phase_pending)
+  // the positions of a pass wait for its crossers (STAGE instances: species sorted by tile only, charge-0 copies) when the
+  // queue fills every other pass anyway -- from a third of the particles crossing per step on (a colder species would pay
+  // for half-empty batches: two drains where one did); VPIC_HIP_STAGE=0|1 overrides
+  pl.stage = in.stage >= 0 ? in.stage : (s.cross_frac > 0.33 ? 1 : 0);
+  // the sort inside the push (Species::fuse_pending) -- not after all when a tile turned out overfull, the next step sorts too and
+  // this push must count for it, ...
+  pl.fuse = in.fuse_pending && pl.tiled && !in.coarse_sorted && in.phase == 0 && !in.det_acc && !in.hist_request && in.hist_valid &&
+            in.fuse_buffers && in.np == in.n_sorted && !in.time_kernels;
+  pl.sort_first = in.fuse_pending && !pl.fuse;
+  const int64_t behind = in.np > in.n_sorted ? in.np - in.n_sorted : 0;
+  pl.regroup_tail = pl.tiled && behind >= in.tail_sort_min && behind > 0 && !in.no_tail_sort;   // a handful costs less pushed as it is (tests lower the threshold)
+  // the histogram of the next sort (Species::hist): tile order by cell, one launch, float sums, no tile anywhere near 2^15 particles
+  pl.hist = !pl.fuse && in.hist_request && pl.tiled && !in.coarse_sorted && in.phase == 0 && !(in.det_acc && !in.chargeless) &&
+            (uint64_t)in.fullest_tile + (uint64_t)behind < 30000u;   // (16-bit counters per window cell: the fullest tile AND whatever share of the appended particles its workgroup takes)
+  // deterministic accumulation: the kernels add into the engine's 64-bit fixed-point accumulator (engine.hip, acc_finalize)
+  pl.det = in.det_acc && !in.chargeless;
+  pl.instance = in.chargeless ? PushInstance::chargeless
+              : pl.det ? (pl.tiled ? (in.coarse_sorted ? PushInstance::det_tile_only : PushInstance::det_tile) : PushInstance::det_row)
+              : !pl.tiled ? (s.wide_window ? PushInstance::row_wide : PushInstance::row_narrow)
+              : in.coarse_sorted ? PushInstance::tile_only : pl.fuse ? PushInstance::tile_sort : pl.hist ? PushInstance::tile_hist : PushInstance::tile;
+  return pl;
+}
+
+}  // namespace vpichip

@@ -1216,7 +1216,7 @@ int k_sort_check(Engine *e, Species &s, const int *starts, int n1) {
   unsigned *word = reinterpret_cast<unsigned *>(e->counters + 201);
   hipLaunchKernelGGL(fuse_clear_kernel, dim3(1), dim3(1), 0, e->stream, word);
   hipLaunchKernelGGL(fuse_check_kernel, dim3((n1 + 255) / 256), dim3(256), 0, e->stream, (const int *)e->sort_next, starts, n1, word);
-  hipLaunchKernelGGL(fuse_publish_kernel, dim3(1), dim3(1), 0, e->stream, s.crossed_host_dev + 2, (const unsigned *)word);
+  hipLaunchKernelGGL(fuse_publish_kernel, dim3(1), dim3(1), 0, e->stream, s.crossed_host_dev + PW_SORT_CHECK, (const unsigned *)word);
   VH_CHECK(hipGetLastError());
   return 0;
 }
@@ -1279,6 +1279,13 @@ static int ensure_tile_lists(Engine *e) {
   return 0;
 }
 
+// one advance_p_kernel instance (policy.h: PushInstance), in the arithmetic Engine::push_fast asks for
+template <bool CHARGELESS, int WIN = 0, bool HIST = false, bool SORT = false>
+static void launch_push(bool fast, unsigned grid, hipStream_t stream, const ParticlesK &p, const float4 *fi, float *g_acc, DrainParams *d, const PushParams &P) {
+  if (fast) hipLaunchKernelGGL((advance_p_kernel<CHARGELESS, true, WIN, HIST, SORT>), dim3(grid), dim3(PUSH_THREADS), 0, stream, p, fi, g_acc, d, P);
+  else hipLaunchKernelGGL((advance_p_kernel<CHARGELESS, false, WIN, HIST, SORT>), dim3(grid), dim3(PUSH_THREADS), 0, stream, p, fi, g_acc, d, P);
+}
+
 // phase 0: the whole species in one launch.  phase 1 / 2 (vpic_hip_advance_p_phase, tile order): first the tiles on the
 // faces this domain shares with others, together with the particles appended since the sort -- every particle that can
 // leave the domain in this step, up to stragglers that drifted into a boundary cell from an interior tile's range since
@@ -1296,11 +1303,9 @@ int k_advance_p(Engine *e, Species &s, bool async, int phase) {
   P.sy = e->gk.sy; P.sz = e->gk.sz;
 #ifdef VPIC_HIP_ABLATION
   P.ablate = e->knobs.ablate;
-  const int ablating = 0;
-#else
-  const int ablating = 0;
 #endif
-  if (s.crossed_host[2]) VH_FAIL("advance_p: %u keys of the species' last sort did not receive the particles the push before it had counted for them", s.crossed_host[2]);
+  const unsigned *pinned = s.crossed_host;    // (read once: the device writes them behind its launches)
+  if (pinned[PW_SORT_CHECK]) VH_FAIL("advance_p: %u keys of the species' last sort did not receive the particles the push before it had counted for them", pinned[PW_SORT_CHECK]);
   if (phase == 2 && !s.phase_pending) return 0;          // phase 1 pushed everything
   if (phase != 2) {
     VH_CHECK(hipMemsetAsync(s.nm_dev, 0, sizeof(int), e->stream));   // (phase 2 appends to what the exchange left on the list)
@@ -1309,37 +1314,23 @@ int k_advance_p(Engine *e, Species &s, bool async, int phase) {
   s.phase_pending = false;
   P.crossed = s.crossed_dev;
   if (s.np > 0) {
-    // particles per cell decide how many 64-particle passes a wavefront makes: a workgroup's chunk
-    // should span a little less than the LDS window (measured, tools/iters_sweep.sh: 32 ppc best at 6
-    // passes, 64 ppc at 12, 512 ppc at 64; one pass too many and the chunk overflows the window)
-    const double ppc = (double)s.np / ((double)e->gk.nx * e->gk.ny * e->gk.nz);
-    // Which window: the crossing fraction of this species' previous launch (a pinned word the device wrote behind
-    // that launch; a stale value only delays the switch) with hysteresis; VPIC_HIP_WINDOW=wide|narrow overrides.
-    if (phase != 2) {
-      const double frac = s.np_pushed_last > 0 ? (double)*s.crossed_host / (double)s.np_pushed_last : 0.0;
-      s.cross_frac = frac;
-      if (frac > 0.30) s.wide_window = true; else if (frac < 0.20) s.wide_window = false;
-      if (e->knobs.window == 'w') s.wide_window = true; else if (e->knobs.window == 'n') s.wide_window = false;
-      if (ablating) s.wide_window = false;
-      s.np_pushed_last = s.np;
-    }
-    const int wx = s.wide_window ? Window<true>::WX : Window<false>::WX;
-    int it = (int)(0.9 * (wx - 2 * WMARGIN) * ppc / PUSH_THREADS);
-    P.iters = it < 1 ? 1 : it > PUSH_ITERS ? PUSH_ITERS : it;
-    if (e->knobs.iters > 0) P.iters = e->knobs.iters;   // tuning experiments
+    // the row window, the passes per wavefront, tiles or rows, which instance (policy.h: push_passes, plan_push)
+    PushInputs in;
+    in.phase = phase; in.np = s.np; in.n_sorted = s.n_sorted; in.ppc = (double)s.np / ((double)e->gk.nx * e->gk.ny * e->gk.nz);
+    in.crossers = pinned[PW_CROSSERS]; in.fullest_tile = pinned[PW_FULLEST_TILE];
+    in.window = e->knobs.window; in.iters = e->knobs.iters; in.stage = e->knobs.stage;
+    in.tail_sort_min = e->knobs.tail_sort_min; in.no_tail_sort = e->knobs.no_tail_sort;
+    in.wx[0] = Window<false>::WX; in.wx[1] = Window<true>::WX; in.wmargin = WMARGIN; in.threads = PUSH_THREADS; in.max_iters = PUSH_ITERS;
+    in.tile_valid = s.tile_valid; in.chargeless = s.chargeless; in.coarse_sorted = s.coarse_sorted; in.det_acc = e->det_acc; in.time_kernels = e->time_kernels;
+    in.fuse_pending = s.fuse_pending; in.hist_request = s.hist_request; in.hist_valid = s.hist_valid; in.fuse_buffers = s.aux.dx && s.tpart2;
+    P.iters = push_passes(s.pol, in);
     int64_t seg_start[4]; int32_t seg_count[4]; uint32_t seg_grid[4];
     const int n_seg = vpic_hip_push_plan(s.np, P.iters, seg_start, seg_count, seg_grid, 4);
     if (n_seg < 1) VH_FAIL("advance_p: cannot plan %lld particles", (long long)s.np);
     // TILE order (the last sort grouped the species by tile, engine.h): one workgroup per tile plus the appended particles
     if (e->time_kernels && phase != 2) { if (!s.ev[0]) for (int i = 0; i < 4; i++) VH_CHECK(hipEventCreate(&s.ev[i])); (void)hipEventRecord(s.ev[0], e->stream); }   // (the regrouping of appended particles below counts as push time for the sort policy)
-    // A tile is one workgroup's work.  When the fullest tile alone would take several times what the whole launch takes
-    // if balanced (1280 workgroups run at a time: 256 CUs x 5), the species is too clumped for tiles: this launch falls
-    // back to the row windows and the next sort to the reference's order.  (The count is the last tile sort's, read from
-    // pinned memory without waiting: a stale value only delays the switch.)
-    // (phase 2 keeps what phase 1 decided: the word is written by the sort's kernels while the host runs ahead of them, and a
-    // flip between the two launches of one push would leave the interior tiles unpushed with the boundary movers on the wire)
-    if (phase != 2 && s.tile_valid && (double)s.crossed_host[1] * 1280.0 > 4.0 * (double)s.np && s.crossed_host[1] > 65536u) s.tile_unbalanced = true;
-    const bool tiled = phase == 2 ? true : (s.tile_valid && !s.tile_unbalanced && !s.chargeless && !ablating && n_seg == 1);   // (phase 2 only runs behind a phase 1 that split the tiles: phase_pending)
+    const PushPlan pl = plan_push(s.pol, in, n_seg);
+    const bool tiled = pl.tiled, fuse = pl.fuse, hist = pl.hist, det = pl.det;
     P.tpart = s.tpart; P.ttail = nullptr; P.n_sorted = (int)s.n_sorted;
     P.tile_list = nullptr; P.n_launch = 0; P.tail_chunks = 0;
     P.nx = e->gk.nx; P.ny = e->gk.ny; P.nz = e->gk.nz;
@@ -1347,16 +1338,10 @@ int k_advance_p(Engine *e, Species &s, bool async, int phase) {
     // per tile: publish_counter_kernel) until the next sort: sampling costs a workgroup a dependent load at its
     // start (1-3 % of the launch).  VPIC_HIP_FOLLOW=0|1 overrides.
     P.follow = e->knobs.follow;
-    // the positions of a pass wait for its crossers (STAGE instances: species sorted by tile only, charge-0 copies) when the
-    // queue fills every other pass anyway -- from a third of the particles crossing per step on (a colder species would pay
-    // for half-empty batches: two drains where one did); VPIC_HIP_STAGE=0|1 overrides
-    P.stage = e->knobs.stage >= 0 ? e->knobs.stage : (s.cross_frac > 0.33 ? 1 : 0);
+    P.stage = pl.stage;
     // the sort inside the push (Species::fuse_pending, set by k_sort_p for this very call)
-    bool fuse = s.fuse_pending;
     s.fuse_pending = false;
-    if (fuse && !(tiled && !s.coarse_sorted && phase == 0 && !e->det_acc && !s.hist_request && s.hist_valid && s.aux.dx && s.tpart2 &&
-                  s.np == s.n_sorted && !e->time_kernels)) {
-      // not after all (a tile turned out overfull, the next step sorts too and this push must count for it, ...): sort the ordinary way, then push
+    if (pl.sort_first) {
       if (k_sort_p(e, s, true, false)) return 1;
       return k_advance_p(e, s, async, phase);
     }
@@ -1368,9 +1353,8 @@ int k_advance_p(Engine *e, Species &s, bool async, int phase) {
       P.ntx = tk.ntx; P.nty = tk.nty; P.ntiles = tk.ntiles;
       P.mul_sy = tk.mul_sy; P.sh_sy = tk.sh_sy; P.mul_sz = tk.mul_sz; P.sh_sz = tk.sh_sz;
       const int64_t behind = s.np > s.n_sorted ? s.np - s.n_sorted : 0;
-      const bool regroup_tail = behind >= e->knobs.tail_sort_min && behind > 0 && !e->knobs.no_tail_sort;   // a handful costs less pushed as it is (tests lower the threshold)
-      if (phase != 2 && regroup_tail && k_tail_sort(e, s)) return 1;
-      if (phase != 2) s.tail_regrouped = regroup_tail && s.tail_sorted;
+      if (phase != 2 && pl.regroup_tail && k_tail_sort(e, s)) return 1;
+      if (phase != 2) s.tail_regrouped = pl.regroup_tail && s.tail_sorted;
       P.ttail = s.tail_regrouped ? s.ttail : nullptr;
       P.n_launch = split ? e->tile_list_n[phase - 1] : tk.ntiles;
       P.tile_list = split ? e->tile_list[phase - 1] : nullptr;
@@ -1379,15 +1363,11 @@ int k_advance_p(Engine *e, Species &s, bool async, int phase) {
       s.phase_pending = split && phase == 1;
     }
     const int ev = begin_profile(e, phase == 2 ? -1 : s.np, fuse ? 1 : 0, (int)(&s - e->species.data()));
-    // deterministic accumulation: the kernels add into the engine's 64-bit fixed-point accumulator (engine.hip, acc_finalize)
-    // the histogram of the next sort (Species::hist): tile order by cell, one launch, float sums, no tile anywhere near 2^15 particles
     if (fuse) {                                            // where every key begins in the new order, and the cursors, from the counts of the push before
       const TileK tk = make_tile_k(e->gk);
       if (k_sort_scan(e, s.hist, s.tpart2, tk.ntiles * TILE_CELLS + 1)) return 1;
       P.out = s.aux; P.next = e->sort_next;
     } else { P.out = ParticlesK{}; P.next = nullptr; }
-    const bool hist = !fuse && s.hist_request && tiled && !s.coarse_sorted && phase == 0 && !(e->det_acc && !s.chargeless) &&
-                      (uint64_t)s.crossed_host[1] + (uint64_t)(s.np > s.n_sorted ? s.np - s.n_sorted : 0) < 30000u;   // (16-bit counters per window cell: the fullest tile AND whatever share of the appended particles its workgroup takes)
     s.hist_request = false; s.hist_valid = false;
     if (hist) {
       const TileK tk = make_tile_k(e->gk);
@@ -1396,28 +1376,27 @@ int k_advance_p(Engine *e, Species &s, bool async, int phase) {
       VH_CHECK(hipMemsetAsync(s.hist, 0, sizeof(int) * n1, e->stream));
       P.hist = s.hist; P.ntz = tk.ntz;
     } else { P.hist = nullptr; P.ntz = fuse ? make_tile_k(e->gk).ntz : 0; }
-    const bool det = e->det_acc && !s.chargeless;
     if (det && acc_prepare_det(e)) return 1;
     P.acc_scale = e->acc_scale;
     float *const g_acc = det ? reinterpret_cast<float *>(e->acc64) : reinterpret_cast<float *>(e->acc);
-#define PUSH_LAUNCH(...) hipLaunchKernelGGL((advance_p_kernel<__VA_ARGS__>), dim3(grid), dim3(PUSH_THREADS), 0, e->stream, \
-                                            ps, reinterpret_cast<const float4 *>(e->fi), g_acc, s.drain_k, P)
+#define PUSH_LAUNCH(...) launch_push<__VA_ARGS__>(e->push_fast, seg_grid[g], e->stream, ps, reinterpret_cast<const float4 *>(e->fi), g_acc, s.drain_k, P); break
     for (int g = 0; g < n_seg; g++) {
       const int64_t at = seg_start[g];
-      const unsigned grid = seg_grid[g];
       ParticlesK ps = s.p;
       ps.dx += at; ps.dy += at; ps.dz += at; ps.i += at; ps.ux += at; ps.uy += at; ps.uz += at; ps.q += at;
       P.np = seg_count[g]; P.idx_base = (int)at;
-      if (s.chargeless) { if (e->push_fast) PUSH_LAUNCH(true, true); else PUSH_LAUNCH(true, false); }
-      else if (det && tiled && s.coarse_sorted) { if (e->push_fast) PUSH_LAUNCH(false, true, 6); else PUSH_LAUNCH(false, false, 6); }
-      else if (det && tiled) { if (e->push_fast) PUSH_LAUNCH(false, true, 4); else PUSH_LAUNCH(false, false, 4); }
-      else if (det) { if (e->push_fast) PUSH_LAUNCH(false, true, 5); else PUSH_LAUNCH(false, false, 5); }
-      else if (tiled && s.coarse_sorted) { if (e->push_fast) PUSH_LAUNCH(false, true, 3); else PUSH_LAUNCH(false, false, 3); }
-      else if (tiled && fuse) { if (e->push_fast) PUSH_LAUNCH(false, true, 2, false, true); else PUSH_LAUNCH(false, false, 2, false, true); }
-      else if (tiled && hist) { if (e->push_fast) PUSH_LAUNCH(false, true, 2, true); else PUSH_LAUNCH(false, false, 2, true); }
-      else if (tiled) { if (e->push_fast) PUSH_LAUNCH(false, true, 2); else PUSH_LAUNCH(false, false, 2); }
-      else if (s.wide_window) { if (e->push_fast) PUSH_LAUNCH(false, true, 1); else PUSH_LAUNCH(false, false, 1); }
-      else { if (e->push_fast) PUSH_LAUNCH(false, true, 0); else PUSH_LAUNCH(false, false, 0); }
+      switch (pl.instance) {
+        case PushInstance::chargeless: PUSH_LAUNCH(true);
+        case PushInstance::det_tile_only: PUSH_LAUNCH(false, 6);
+        case PushInstance::det_tile: PUSH_LAUNCH(false, 4);
+        case PushInstance::det_row: PUSH_LAUNCH(false, 5);
+        case PushInstance::tile_only: PUSH_LAUNCH(false, 3);
+        case PushInstance::tile_sort: PUSH_LAUNCH(false, 2, false, true);
+        case PushInstance::tile_hist: PUSH_LAUNCH(false, 2, true);
+        case PushInstance::tile: PUSH_LAUNCH(false, 2);
+        case PushInstance::row_wide: PUSH_LAUNCH(false, 1);
+        case PushInstance::row_narrow: PUSH_LAUNCH(false, 0);
+      }
     }
 #undef PUSH_LAUNCH
     if (ev >= 0) (void)hipEventRecord(e->ev_pool[ev].second, e->stream);
@@ -1434,7 +1413,7 @@ int k_advance_p(Engine *e, Species &s, bool async, int phase) {
       // dependent load at its start -- the two meet there, measured at 32 and 64 particles per cell)
       // (a launch that sorted as it pushed deposited through the windows of the OLD order: its misses say nothing about the new
       // one -- they are published under the old cycle's number, which vpic_hip_step's early sort ignores, and switch nothing on)
-      hipLaunchKernelGGL(publish_counter_kernel, dim3(1), dim3(256), 0, e->stream, s.crossed_host_dev, s.crossed_dev, (unsigned)(s.n_cycle - (fuse ? 1 : 0)),
+      hipLaunchKernelGGL(publish_counter_kernel, dim3(1), dim3(256), 0, e->stream, s.crossed_host_dev, s.crossed_dev, (unsigned)(s.pol.n_cycle - (fuse ? 1 : 0)),
                          fuse ? ~0ull : (unsigned long long)e->knobs.follow_from * (unsigned long long)make_tile_k(e->gk).ntiles);
       if (e->time_kernels) { (void)hipEventRecord(s.ev[1], e->stream); s.push_timed = true; }
     }
