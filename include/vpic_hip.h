@@ -256,6 +256,50 @@ int vpic_hip_sort_advance_p(vpic_hip_engine_t *e, int sp);
  * makes the sort count for itself again. */
 int vpic_hip_species_sort_hint(vpic_hip_engine_t *e, int sp);          /* species_advance/standard/sort_p.c:16-102 */
 int vpic_hip_energy_p(vpic_hip_engine_t *e, int sp, double *energy); /* species_advance/standard/energy_p.cxx:124-157 (local part) */
+
+/* ---- energy spectra of a species (the diagnostic of decks/trecon-part/energy.cxx, computed where the particles are) ----
+ * One pass over the species' stored momenta (no half-step field correction, unlike energy_p).  Per live particle
+ * (dead slots are skipped, particles appended since the last sort are included), energy.cxx:96-108 restated:
+ *   ke   = sqrt(((1 + ux^2) + uy^2) + uz^2) - 1, the float momenta promoted to double, every operation in double, unfused
+ *          (energy.cxx:99 as C++ evaluates it squares in float first: a particle within a float rounding, about 1e-7
+ *          relative, of a band or bin edge may be counted next door there)
+ *   band = (int)(ke / d_lin), clamped to n_lin - 1                       (:102-104, counted in the particle's voxel)
+ *   bin  = (int)((log10(ke) - log_lo) / d_log + 1), counted when 0 <= bin <= n_log - 1   (:107-108)
+ * The conversion to int truncates toward zero, so bin 0 also collects values in (-1, 0); ke == 0 counts in no bin.
+ * The caller computes the constants (the deck mixes float and double in them: dke = emax * (vth * vth / 2.0) / nex,
+ * log_lo = log10(eminp) of a float eminp, dloge a float) and hands them over as doubles.
+ * Counts are integers: the result is the same bit for bit whatever order the array is in and whichever kernel
+ * pushed it.  The reference counts in float (dist[...]++, edist[k]++), which stops increasing at 2^24; the helper of
+ * the deck host (vpic_simulation::energy_spectrum) converts these counts to float, so its output equals the
+ * reference's only while every count is below 2^24 -- above that, this one is the correct one. */
+typedef struct {
+  int32_t n_lin;   /* linear bands per voxel (the deck's nex); 0: none            */
+  int32_t n_log;   /* bins of the log spectrum (the deck's nbin = 800); 0: none  */
+  double  d_lin;   /* band width in units of ke (the deck's dke)                 */
+  double  log_lo;  /* log10 of the lowest energy, as the caller computed it      */
+  double  d_log;   /* bin width in log10(ke) (the deck's dloge, promoted)        */
+} vpic_hip_spectrum_t;
+VPIC_HIP_STATIC_ASSERT(sizeof(vpic_hip_spectrum_t) == 32, "vpic_hip_spectrum_t layout");
+/* most log bins a call takes: a workgroup keeps them as 32-bit counters in LDS (16 KB) beside its four wavefronts'
+ * windows of linear bands (up to 12 KB each) */
+#define VPIC_HIP_SPECTRUM_MAX_LOG 4096
+/* counts only: lin_counts[k*nv + voxel] (uint32, n_lin*nv, ghosts zero), log_counts[n_log] (uint64); host arrays,
+ * either may be NULL (that part is then not computed).  Fails on a bad sp, a NULL s, a negative count, a width that
+ * is not positive, or n_log above VPIC_HIP_SPECTRUM_MAX_LOG. */
+int vpic_hip_energy_spectrum(vpic_hip_engine_t *e, int sp, const vpic_hip_spectrum_t *s,
+                             uint32_t *lin_counts, uint64_t *log_counts);
+/* the per-voxel bands as energy.cxx writes them (:116-162): float bands[k*nv + voxel] = (float)((double)count /
+ * (double)n_voxel), n_voxel the sum of the voxel's bands (0 where that is 0); then every ghost voxel takes the
+ * bands of the interior voxel that clamping each of its indices into [1, n] gives.  (The reference's loop normalises and
+ * copies in one sweep, so a ghost on a LOW face copies its neighbour before that one has been normalised and keeps raw
+ * counts; here every ghost holds normalised bands.)  n_log is ignored. */
+int vpic_hip_energy_bands(vpic_hip_engine_t *e, int sp, const vpic_hip_spectrum_t *s, float *bands);
+/* the last call of either: out[0] particles counted, out[1] particles whose linear band was added in global memory
+ * because their voxel was outside the LDS window of their wavefront (spectrum.hip).  0 for a species in voxel or tile
+ * order whose every 64 consecutive particles lie within 64 sort keys (within two consecutive tiles when it is sorted by
+ * tile only); particles that moved or were appended since the sort may miss, an array in no order misses almost
+ * always, more than 48 bands have no window and always miss.  Misses cost time, never the result. */
+int vpic_hip_energy_spectrum_stats(vpic_hip_engine_t *e, int64_t out[2]);
 int vpic_hip_center_p(vpic_hip_engine_t *e, int sp);        /* species_advance/standard/center_p.cxx: u(-1/2) -> u(0) */
 int vpic_hip_uncenter_p(vpic_hip_engine_t *e, int sp);      /* species_advance/standard/uncenter_p.cxx:154-177: u(0) -> u(-1/2) */
 int vpic_hip_clear_jf(vpic_hip_engine_t *e);                /* field_advance/standard/sfa.c:188-211 */

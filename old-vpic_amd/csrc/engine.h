@@ -231,6 +231,12 @@ struct Engine {
   // start, and pushes the second behind it
   int *tile_list[2] = {nullptr, nullptr}; int tile_list_n[2] = {0, 0};
 
+  // energy spectra (spectrum.hip), allocated by the first call: the linear bands' counters and their normalised form
+  // (n_lin x nv), the log bins, {particles counted, window misses} of the last call, and the pinned words both are read through
+  unsigned *spec_lin = nullptr; float *spec_bands = nullptr; size_t spec_lin_words = 0;
+  unsigned long long *spec_log = nullptr, *spec_stats = nullptr, *spec_host = nullptr;
+  int64_t spec_last[2] = {0, 0};
+
   hipEvent_t step_done[4] = {}; int64_t steps_enqueued = 0;   // vpic_hip_step: the host stays at most two steps ahead of the device
   // profiling
   bool profile = false;
@@ -309,6 +315,8 @@ int k_particles_to_aos(Engine *e, Species &s, vpic_particle_t *host, int64_t cap
 int k_load_maxwellian(Engine *e, Species &s, int ppc, unsigned seed, float q, float ux, float uy, float uz, float vth);
 int k_energy_p(Engine *e, Species &s, double *energy);
 int k_center_p(Engine *e, Species &s, bool uncenter);
+int k_energy_spectrum(Engine *e, Species &s, const vpic_hip_spectrum_t &sp);   // into Engine::spec_lin / spec_log; waits for the stream
+int k_energy_bands(Engine *e, int n_lin);                                        // Engine::spec_lin -> spec_bands
 int k_sort_p(Engine *e, Species &s, bool tile_order = false, bool may_fuse = false);   // may_fuse: the caller pushes the species next (see Species::fuse_pending)
 int k_sort_scan(Engine *e, const int *counts, int *starts, int n1);                  // exclusive scan of counts[0..n1) into starts[] and Engine::sort_next[]
 int k_sort_check(Engine *e, Species &s, const int *starts, int n1);                    // every cursor ended where the next key begins? (PW_SORT_CHECK; the next push fails loudly otherwise)

@@ -196,6 +196,7 @@ static void destroy(Engine *e) {
   (void)hipFree(e->sp_table_dev); (void)hipHostFree(e->sp_table_host); (void)hipFree(e->xmsg_dev); (void)hipHostFree(e->xmsg_host);
   (void)hipFree(e->retry_buf); (void)hipFree(e->tile_list[0]); (void)hipFree(e->tile_list[1]);
   (void)hipFree(e->acc64); (void)hipFree(e->rho64);
+  (void)hipFree(e->spec_lin); (void)hipFree(e->spec_bands); (void)hipFree(e->spec_log); (void)hipFree(e->spec_stats); (void)hipHostFree(e->spec_host);
   for (auto &ev : e->ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
   for (auto ev : e->step_done) if (ev) (void)hipEventDestroy(ev);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -651,6 +652,47 @@ int vpic_hip_energy_p(vpic_hip_engine_t *e, int sp, double *energy) {
   ENGINE(e); SPECIES(e, sp);
   if (!energy) VH_FAIL("Bad energy");
   return k_energy_p(e, e->species[sp], energy);
+}
+static int check_spectrum(const vpic_hip_spectrum_t *s, bool need_lin) {
+  if (!s) VH_FAIL("Bad spectrum parameters");
+  if (s->n_lin < 0 || s->n_log < 0) VH_FAIL("energy spectrum: negative count (n_lin %d, n_log %d)", s->n_lin, s->n_log);
+  if (s->n_log > VPIC_HIP_SPECTRUM_MAX_LOG) VH_FAIL("energy spectrum: n_log %d above the cap of %d", s->n_log, VPIC_HIP_SPECTRUM_MAX_LOG);
+  if (need_lin && s->n_lin == 0) VH_FAIL("energy bands: n_lin is 0");
+  if (s->n_lin > 0 && !(s->d_lin > 0)) VH_FAIL("energy spectrum: band width %g", s->d_lin);
+  if (s->n_log > 0 && !(s->d_log > 0)) VH_FAIL("energy spectrum: log bin width %g", s->d_log);
+  return 0;
+}
+int vpic_hip_energy_spectrum(vpic_hip_engine_t *e, int sp, const vpic_hip_spectrum_t *s, uint32_t *lin_counts, uint64_t *log_counts) {
+  ENGINE(e); SPECIES(e, sp);
+  if (check_spectrum(s, false)) return 1;
+  vpic_hip_spectrum_t want = *s;                          // (a part whose array is NULL is not computed)
+  if (!lin_counts) want.n_lin = 0;
+  if (!log_counts) want.n_log = 0;
+  const size_t lin_bytes = sizeof(uint32_t) * (size_t)want.n_lin * (size_t)e->gk.nv;
+  host_will_write(lin_counts, lin_bytes);
+  host_will_write(log_counts, sizeof(uint64_t) * (size_t)want.n_log);
+  if (k_energy_spectrum(e, e->species[sp], want)) return 1;
+  if (lin_bytes) VH_CHECK(hipMemcpy(lin_counts, e->spec_lin, lin_bytes, hipMemcpyDeviceToHost));
+  if (want.n_log) memcpy(log_counts, e->spec_host + 2, sizeof(uint64_t) * (size_t)want.n_log);
+  return 0;
+}
+int vpic_hip_energy_bands(vpic_hip_engine_t *e, int sp, const vpic_hip_spectrum_t *s, float *bands) {
+  ENGINE(e); SPECIES(e, sp);
+  if (check_spectrum(s, true)) return 1;
+  if (!bands) VH_FAIL("Bad bands array");
+  vpic_hip_spectrum_t want = *s;
+  want.n_log = 0;
+  const size_t bytes = sizeof(float) * (size_t)want.n_lin * (size_t)e->gk.nv;
+  host_will_write(bands, bytes);
+  if (k_energy_spectrum(e, e->species[sp], want) || k_energy_bands(e, want.n_lin)) return 1;
+  VH_CHECK(hipMemcpyAsync(bands, e->spec_bands, bytes, hipMemcpyDeviceToHost, e->stream));
+  VH_CHECK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+int vpic_hip_energy_spectrum_stats(vpic_hip_engine_t *e, int64_t out[2]) {
+  ENGINE(e); if (!out) VH_FAIL("Bad output");
+  out[0] = e->spec_last[0]; out[1] = e->spec_last[1];
+  return 0;
 }
 int vpic_hip_center_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp); return k_center_p(e, e->species[sp], false); }
 int vpic_hip_uncenter_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp); return k_center_p(e, e->species[sp], true); }

@@ -32,6 +32,11 @@ class GridDesc(C.Structure):
         return L.nv(self.nx, self.ny, self.nz)
 
 
+class SpectrumParams(C.Structure):
+    """vpic_hip_spectrum_t (include/vpic_hip.h)"""
+    _fields_ = [("n_lin", C.c_int32), ("n_log", C.c_int32), ("d_lin", C.c_double), ("log_lo", C.c_double), ("d_log", C.c_double)]
+
+
 def make_grid(nx, ny, nz, lx, ly, lz, dt, cvac=1.0, eps0=1.0, damp=0.0, fbc=None, pbc=None, rank=0):
     """A box domain.  Cell sizes are formed as partition_periodic_box does
     (src/grid/partition.c:60-66): double arithmetic, stored as float."""
@@ -298,6 +303,31 @@ class Engine:
         e = C.c_double()
         self._ck(self._l.vpic_hip_energy_p(self._h, sp, C.byref(e)))
         return e.value
+
+    # ---- energy spectra (include/vpic_hip.h: vpic_hip_energy_spectrum) ----
+    def energy_spectrum(self, sp, n_lin=0, d_lin=0.0, n_log=0, log_lo=0.0, d_log=0.0):
+        """(lin_counts[n_lin, nv] uint32, log_counts[n_log] uint64) of the species' kinetic energies; None for a part
+        not asked for (n_lin == 0 / n_log == 0)."""
+        prm = SpectrumParams(int(n_lin), int(n_log), float(d_lin), float(log_lo), float(d_log))
+        lin = np.zeros((n_lin, self.nv), np.uint32) if n_lin > 0 else None
+        log = np.zeros(n_log, np.uint64) if n_log > 0 else None
+        self._ck(self._l.vpic_hip_energy_spectrum(self._h, int(sp), C.byref(prm), _ptr(lin) if n_lin > 0 else None,
+                                                  _ptr(log) if n_log > 0 else None))
+        return lin, log
+
+    def energy_bands(self, sp, n_lin, d_lin):
+        """float32[n_lin, nv]: every voxel's share of its particles per linear energy band, ghost voxels filled from
+        their interior neighbours (what the production deck's energy diagnostic writes)."""
+        prm = SpectrumParams(int(n_lin), 0, float(d_lin), 0.0, 0.0)
+        bands = np.zeros((max(int(n_lin), 0), self.nv), np.float32)
+        self._ck(self._l.vpic_hip_energy_bands(self._h, int(sp), C.byref(prm), _ptr(bands)))
+        return bands
+
+    def energy_spectrum_stats(self):
+        """(particles counted, window misses) of the last energy_spectrum / energy_bands call."""
+        out = (C.c_int64 * 2)()
+        self._ck(self._l.vpic_hip_energy_spectrum_stats(self._h, out))
+        return int(out[0]), int(out[1])
 
     def center_p(self, sp):
         self._ck(self._l.vpic_hip_center_p(self._h, sp))

@@ -567,6 +567,7 @@ void vpic_simulation::describe(vpic_hip_grid_t &d) {
   }
 }
 
+static int64_t g_particle_downloads = 0;     // whole-species downloads into the host mirrors (vpic_simulation::particle_mirror_downloads)
 int vpic_simulation::resident_id(const particle_t *p0) const {
   if (!engine) return -1;
   for (size_t k = 0; k < species_order.size(); k++) if (species_order[k]->p == p0) return (int)k;
@@ -584,6 +585,20 @@ double vpic_simulation::resident_energy_p(const particle_t *p0) {
   }
   return 0;
 }
+void vpic_simulation::energy_spectrum(species_t *sp, int nex, double dke, float *bands, int nbin, double log_lo, double dloge, float *spectrum) {
+  if (!sp) ERROR(("Invalid species"));
+  const int id = resident_id(sp->p);
+  if (!engine || id < 0) ERROR(("energy_spectrum before the run has started is not supported by this host"));
+  vpic_hip_spectrum_t s;
+  s.n_lin = nex; s.n_log = nbin; s.d_lin = dke; s.log_lo = log_lo; s.d_log = dloge;
+  if (bands && nex > 0) CK(vpic_hip_energy_bands(engine, id, &s, bands));
+  if (spectrum && nbin > 0) {
+    std::vector<uint64_t> counts((size_t)nbin);
+    CK(vpic_hip_energy_spectrum(engine, id, &s, NULL, &counts[0]));
+    for (int k = 0; k < nbin; k++) spectrum[k] = (float)counts[k];
+  }
+}
+int64_t vpic_simulation::particle_mirror_downloads(void) const { return g_particle_downloads; }
 bool vpic_simulation::resident_energy_f(double *en, const field_t *f) {
   if (!engine || f != field) return false;
   CK(vpic_hip_energy_f(engine, en));
@@ -607,6 +622,7 @@ void vpic_simulation::mirror_download(int kind, int sp) {
     if (np > s->max_np) ERROR(("species %s outgrew its host mirror", s->name));
     CK(vpic_hip_species_get_particles(engine, sp, s->p, s->max_np));
     s->np = (int)np;
+    g_particle_downloads++;
   }
 }
 // demand mode, after the engine changed state: counts are cheap to keep current, arrays become inaccessible
@@ -675,6 +691,7 @@ void vpic_simulation::hip_sync_mirrors(void) {
     if (np > sp->max_np) ERROR(("species %s outgrew its host mirror", sp->name));
     CK(vpic_hip_species_get_particles(engine, (int)k, sp->p, sp->max_np));
     sp->np = (int)np; sp->nm = 0;
+    g_particle_downloads++;
   }
   mirrors_current = true;
 }

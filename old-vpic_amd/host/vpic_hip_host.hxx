@@ -296,6 +296,15 @@ public:
   void resident_advance_p(int id);                  // push one resident species; its movers wait for ...
   void resident_boundary_p(void);                   // ... the exchange of every resident species with pending movers
   double resident_energy_p(const particle_t *p0);
+  // The energy diagnostic of the production deck (decks/trecon-part/energy.cxx:89-162) from the resident state, in place
+  // of a loop over sp->p, which would download the whole species: bands[k * nv + voxel] (nex * nv floats, or NULL) the
+  // share of the voxel's particles in each of nex linear bands of width dke, ghost voxels filled from their interior
+  // neighbours; spectrum[k] (nbin floats, or NULL) the particles per bin of width dloge in log10(ke) above log_lo =
+  // log10(eminp).  The particle mirror does not become resident.  Counted as include/vpic_hip.h says
+  // (vpic_hip_energy_spectrum): in integers -- the floats written here equal the reference's while every count is
+  // below 2^24, where the reference's float counters stop.  Only once the run has started (the engine owns the particles).
+  void energy_spectrum(species_t *sp, int nex, double dke, float *bands, int nbin, double log_lo, double dloge, float *spectrum);
+  int64_t particle_mirror_downloads(void) const;    // whole-species downloads into the host mirrors so far (diagnostics, tests)
   bool resident_energy_f(double *en, const field_t *f);
 
 private:
