@@ -300,6 +300,63 @@ int vpic_hip_energy_bands(vpic_hip_engine_t *e, int sp, const vpic_hip_spectrum_
  * tile only); particles that moved or were appended since the sort may miss, an array in no order misses almost
  * always, more than 48 bands have no window and always miss.  Misses cost time, never the result. */
 int vpic_hip_energy_spectrum_stats(vpic_hip_engine_t *e, int64_t out[2]);
+
+/* ---- phase-space distributions of a species: a 1-D or 2-D histogram over position, momentum and kinetic energy,
+ * optionally of the particles inside a region, computed where the particles are (csrc/distribution.hip) ----
+ * One pass over those of the species' arrays that the descriptor names (x-ux reads i, dx, ux: 12 B per particle).
+ * Everything below is IEEE double, every operation rounded once, unfused.  Per live particle -- 0 <= i < nv; dead
+ * slots (i = -1) are skipped, particles appended since the last sort are included:
+ *   X, Y, Z   position in cells from the low corner of the domain's interior: the voxel i = cx + sy * (cy + (ny+2) * cz),
+ *             sy = nx + 2, is decoded, and X = (double)(cx - 1) + ((double)dx + 1.0) * 0.5; Y and Z likewise.  X lies in
+ *             [0, nx]; a particle whose voxel is in a ghost layer falls outside that interval by the same formula.  The
+ *             units are local cells because vpic_hip_grid_t has no origin: the caller folds the origin and the cell size
+ *             into lo and d (vpic_simulation::distribution of the deck host does, from physical units).
+ *   UX, UY, UZ the stored float momenta promoted to double
+ *   KE        sqrt(((1 + ux^2) + uy^2) + uz^2) - 1 with the promoted momenta (as vpic_hip_energy_spectrum)
+ *   LOG10_KE  log10(KE); KE == 0 gives -inf, which lies in no bin
+ * Selection: the particle is kept when lo <= c < hi holds for every one of the n_sel ranges (0 to 4 of them).
+ * Bin: per axis t = (c - lo) / d; a kept particle is counted when t >= 0 && t < n on every axis (so a NaN is never
+ * counted), in bin (int)t.  Nothing is clamped into the end bins.  counts[b1 * n0 + b0], n1 = 1 when n_axes == 1.
+ * Counters are integers (32-bit per workgroup or wavefront in LDS, 64-bit in global memory): the result is the same
+ * bit for bit whatever order the array is in and whichever kernel pushed it. */
+enum { VPIC_HIP_COORD_X = 0, VPIC_HIP_COORD_Y, VPIC_HIP_COORD_Z,
+       VPIC_HIP_COORD_UX, VPIC_HIP_COORD_UY, VPIC_HIP_COORD_UZ,
+       VPIC_HIP_COORD_KE, VPIC_HIP_COORD_LOG10_KE };
+typedef struct { int32_t coord, n; double lo, d; } vpic_hip_dist_axis_t;        /* n bins of width d from lo */
+typedef struct { int32_t coord, pad; double lo, hi; } vpic_hip_dist_range_t;    /* keep particles with lo <= c < hi */
+typedef struct {
+  int32_t n_axes, n_sel;                  /* 1 or 2 axes; 0 to 4 ranges */
+  vpic_hip_dist_axis_t axis[2];
+  vpic_hip_dist_range_t sel[4];
+} vpic_hip_dist_t;
+VPIC_HIP_STATIC_ASSERT(sizeof(vpic_hip_dist_axis_t) == 24 && sizeof(vpic_hip_dist_range_t) == 24 && sizeof(vpic_hip_dist_t) == 152,
+                       "vpic_hip_dist_t layout");
+#define VPIC_HIP_DIST_MAX_BINS (1 << 22)     /* n0 * n1: 32 MB of uint64 at the most */
+/* Up to this many bins (n0 * n1) every workgroup keeps the whole histogram in its LDS as 32-bit counters and adds
+ * it to global memory once, at the end: 32 KB, so that five workgroups of four wavefronts share a CU's 160 KB. */
+#define VPIC_HIP_DIST_LDS_BINS 8192
+/* counts: n0 * n1 uint64 in host memory.  Fails (non-zero, vpic_hip_last_error) on a bad sp, a NULL d or counts,
+ * n_axes other than 1 or 2, n_sel outside 0..4, an unknown coordinate, n < 1, a d that is not positive and finite,
+ * or n0 * n1 above VPIC_HIP_DIST_MAX_BINS. */
+int vpic_hip_species_distribution(vpic_hip_engine_t *e, int sp, const vpic_hip_dist_t *d, uint64_t *counts);
+/* The last call: out[0] live particles seen, out[1] particles kept by the selection, out[2] particles counted (the
+ * sum of counts), out[3] particles added through global memory because their bin was outside what their workgroup or
+ * wavefront held in LDS.  Three paths (distribution.hip):
+ *   n0 * n1 <= VPIC_HIP_DIST_LDS_BINS: the whole histogram is in LDS, out[3] is 0 always.
+ *   Larger, and an axis is X, Y or Z (the first such axis is "the position axis", of width d cells per bin): every
+ *     wavefront keeps an LDS window of W consecutive bins of the position axis by all bins of the other axis, W at least
+ *     the ceil(4 / d) + 1 bins that the four cells of a tile can touch, and moves it to the first bin of the tile its
+ *     particles are in, at most twice per 64 particles.  This path is taken when W x the other axis' bins fit in 3072
+ *     words, which they do for a position axis with bins one cell wide or wider and up to 512 bins on the other axis
+ *     (half a cell: 256).  Then out[3] is 0 for a species in voxel order or in tile order (by cell or by tile only)
+ *     whose every 64 consecutive particles lie in at most two voxels (two tiles when sorted by tile only) -- at least
+ *     64 particles in every occupied voxel is enough.  Particles that moved or were appended since the sort may miss;
+ *     an array in no order misses almost always.  (A species in tile order is walked tile by tile, the tiles that share
+ *     their bins of the position axis by the same wavefront; the rule is the same.)
+ *   Otherwise (a large momentum-momentum histogram, position bins too fine for a window): every counted particle is
+ *     added in global memory, the lanes of a wavefront that share a bin adding once together, and out[3] == out[2].
+ * Misses cost time, never the result. */
+int vpic_hip_species_distribution_stats(vpic_hip_engine_t *e, int64_t out[4]);
 int vpic_hip_center_p(vpic_hip_engine_t *e, int sp);        /* species_advance/standard/center_p.cxx: u(-1/2) -> u(0) */
 int vpic_hip_uncenter_p(vpic_hip_engine_t *e, int sp);      /* species_advance/standard/uncenter_p.cxx:154-177: u(0) -> u(-1/2) */
 int vpic_hip_clear_jf(vpic_hip_engine_t *e);                /* field_advance/standard/sfa.c:188-211 */

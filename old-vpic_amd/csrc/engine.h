@@ -236,6 +236,10 @@ struct Engine {
   unsigned *spec_lin = nullptr; float *spec_bands = nullptr; size_t spec_lin_words = 0;
   unsigned long long *spec_log = nullptr, *spec_stats = nullptr, *spec_host = nullptr;
   int64_t spec_last[2] = {0, 0};
+  // phase-space distributions (distribution.hip), allocated by the first call and grown on demand: the counters, the four
+  // statistics of the last call, and the pinned buffer {statistics, counters} both come back through
+  unsigned long long *dist_counts = nullptr, *dist_stats = nullptr, *dist_host = nullptr; size_t dist_bins = 0;
+  int64_t dist_last[4] = {0, 0, 0, 0};
 
   hipEvent_t step_done[4] = {}; int64_t steps_enqueued = 0;   // vpic_hip_step: the host stays at most two steps ahead of the device
   // profiling
@@ -317,6 +321,7 @@ int k_energy_p(Engine *e, Species &s, double *energy);
 int k_center_p(Engine *e, Species &s, bool uncenter);
 int k_energy_spectrum(Engine *e, Species &s, const vpic_hip_spectrum_t &sp);   // into Engine::spec_lin / spec_log; waits for the stream
 int k_energy_bands(Engine *e, int n_lin);                                        // Engine::spec_lin -> spec_bands
+int k_species_distribution(Engine *e, Species &s, const vpic_hip_dist_t &d);     // into Engine::dist_counts / dist_host; waits for the stream
 int k_sort_p(Engine *e, Species &s, bool tile_order = false, bool may_fuse = false);   // may_fuse: the caller pushes the species next (see Species::fuse_pending)
 int k_sort_scan(Engine *e, const int *counts, int *starts, int n1);                  // exclusive scan of counts[0..n1) into starts[] and Engine::sort_next[]
 int k_sort_check(Engine *e, Species &s, const int *starts, int n1);                    // every cursor ended where the next key begins? (PW_SORT_CHECK; the next push fails loudly otherwise)

@@ -197,6 +197,7 @@ static void destroy(Engine *e) {
   (void)hipFree(e->retry_buf); (void)hipFree(e->tile_list[0]); (void)hipFree(e->tile_list[1]);
   (void)hipFree(e->acc64); (void)hipFree(e->rho64);
   (void)hipFree(e->spec_lin); (void)hipFree(e->spec_bands); (void)hipFree(e->spec_log); (void)hipFree(e->spec_stats); (void)hipHostFree(e->spec_host);
+  (void)hipFree(e->dist_counts); (void)hipFree(e->dist_stats); (void)hipHostFree(e->dist_host);
   for (auto &ev : e->ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
   for (auto ev : e->step_done) if (ev) (void)hipEventDestroy(ev);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -692,6 +693,34 @@ int vpic_hip_energy_bands(vpic_hip_engine_t *e, int sp, const vpic_hip_spectrum_
 int vpic_hip_energy_spectrum_stats(vpic_hip_engine_t *e, int64_t out[2]) {
   ENGINE(e); if (!out) VH_FAIL("Bad output");
   out[0] = e->spec_last[0]; out[1] = e->spec_last[1];
+  return 0;
+}
+int vpic_hip_species_distribution(vpic_hip_engine_t *e, int sp, const vpic_hip_dist_t *d, uint64_t *counts) {
+  ENGINE(e); SPECIES(e, sp);
+  if (!d) VH_FAIL("Bad distribution descriptor");
+  if (!counts) VH_FAIL("Bad counts array");
+  if (d->n_axes != 1 && d->n_axes != 2) VH_FAIL("distribution: %d axes (1 or 2)", d->n_axes);
+  if (d->n_sel < 0 || d->n_sel > 4) VH_FAIL("distribution: %d ranges (0 to 4)", d->n_sel);
+  long long bins = 1;
+  for (int a = 0; a < d->n_axes; a++) {
+    const vpic_hip_dist_axis_t &x = d->axis[a];
+    if (x.coord < VPIC_HIP_COORD_X || x.coord > VPIC_HIP_COORD_LOG10_KE) VH_FAIL("distribution: unknown coordinate %d of axis %d", x.coord, a);
+    if (x.n < 1) VH_FAIL("distribution: %d bins on axis %d", x.n, a);
+    if (!(x.d > 0) || !std::isfinite(x.d)) VH_FAIL("distribution: bin width %g of axis %d", x.d, a);
+    bins *= x.n;                                            // (at most 2^62)
+  }
+  for (int s = 0; s < d->n_sel; s++)
+    if (d->sel[s].coord < VPIC_HIP_COORD_X || d->sel[s].coord > VPIC_HIP_COORD_LOG10_KE) VH_FAIL("distribution: unknown coordinate %d of range %d", d->sel[s].coord, s);
+  if (bins > VPIC_HIP_DIST_MAX_BINS) VH_FAIL("distribution: %lld bins above the cap of %d", bins, VPIC_HIP_DIST_MAX_BINS);
+  const size_t bytes = sizeof(uint64_t) * (size_t)bins;
+  host_will_write(counts, bytes);
+  if (k_species_distribution(e, e->species[sp], *d)) return 1;
+  memcpy(counts, e->dist_host + 4, bytes);
+  return 0;
+}
+int vpic_hip_species_distribution_stats(vpic_hip_engine_t *e, int64_t out[4]) {
+  ENGINE(e); if (!out) VH_FAIL("Bad output");
+  for (int j = 0; j < 4; j++) out[j] = e->dist_last[j];
   return 0;
 }
 int vpic_hip_center_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp); return k_center_p(e, e->species[sp], false); }

@@ -37,6 +37,39 @@ class SpectrumParams(C.Structure):
     _fields_ = [("n_lin", C.c_int32), ("n_log", C.c_int32), ("d_lin", C.c_double), ("log_lo", C.c_double), ("d_log", C.c_double)]
 
 
+class DistAxis(C.Structure):
+    """vpic_hip_dist_axis_t"""
+    _fields_ = [("coord", C.c_int32), ("n", C.c_int32), ("lo", C.c_double), ("d", C.c_double)]
+
+
+class DistRange(C.Structure):
+    """vpic_hip_dist_range_t"""
+    _fields_ = [("coord", C.c_int32), ("pad", C.c_int32), ("lo", C.c_double), ("hi", C.c_double)]
+
+
+class DistDesc(C.Structure):
+    """vpic_hip_dist_t (include/vpic_hip.h)"""
+    _fields_ = [("n_axes", C.c_int32), ("n_sel", C.c_int32), ("axis", DistAxis * 2), ("sel", DistRange * 4)]
+
+
+assert C.sizeof(DistDesc) == 152
+DIST_COORDS = {"x": 0, "y": 1, "z": 2, "ux": 3, "uy": 4, "uz": 5, "ke": 6, "log10_ke": 7}    # VPIC_HIP_COORD_*
+DIST_MAX_BINS, DIST_LDS_BINS = 1 << 22, 8192                                                   # VPIC_HIP_DIST_*
+
+
+def dist_desc(axes, select=()):
+    """vpic_hip_dist_t of one or two (coord, lo, d, n) axes and up to four (coord, lo, hi) ranges, coordinates by name."""
+    axes, select = list(axes), list(select)
+    if len(axes) not in (1, 2) or len(select) > 4:
+        raise ValueError("distribution: one or two axes and at most four ranges")
+    d = DistDesc(len(axes), len(select))
+    for k, (coord, lo, width, n) in enumerate(axes):
+        d.axis[k] = DistAxis(DIST_COORDS[coord], int(n), float(lo), float(width))
+    for k, (coord, lo, hi) in enumerate(select):
+        d.sel[k] = DistRange(DIST_COORDS[coord], 0, float(lo), float(hi))
+    return d
+
+
 def make_grid(nx, ny, nz, lx, ly, lz, dt, cvac=1.0, eps0=1.0, damp=0.0, fbc=None, pbc=None, rank=0):
     """A box domain.  Cell sizes are formed as partition_periodic_box does
     (src/grid/partition.c:60-66): double arithmetic, stored as float."""
@@ -328,6 +361,23 @@ class Engine:
         out = (C.c_int64 * 2)()
         self._ck(self._l.vpic_hip_energy_spectrum_stats(self._h, out))
         return int(out[0]), int(out[1])
+
+    # ---- phase-space distributions (include/vpic_hip.h: vpic_hip_species_distribution) ----
+    def distribution(self, sp, axes, select=()):
+        """uint64[n0] or uint64[n1, n0]: the histogram of the species over one or two axes (coord, lo, d, n) -- n bins of
+        width d from lo; coord one of "x", "y", "z" (cells from the low corner of the interior), "ux", "uy", "uz", "ke",
+        "log10_ke" -- of the particles inside every (coord, lo, hi) range of `select`."""
+        d = dist_desc(axes, select)
+        n0, n1 = max(d.axis[0].n, 0), max(d.axis[1].n, 0) if d.n_axes == 2 else 1
+        counts = np.zeros(min(n0 * n1, DIST_MAX_BINS), np.uint64)        # (a descriptor the library refuses is refused below)
+        self._ck(self._l.vpic_hip_species_distribution(self._h, int(sp), C.byref(d), _ptr(counts) if counts.size else None))
+        return counts.reshape(n1, n0) if d.n_axes == 2 else counts
+
+    def distribution_stats(self):
+        """(live particles seen, kept by the selection, counted, added through global memory) of the last distribution call."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._l.vpic_hip_species_distribution_stats(self._h, out))
+        return tuple(int(v) for v in out)
 
     def center_p(self, sp):
         self._ck(self._l.vpic_hip_center_p(self._h, sp))

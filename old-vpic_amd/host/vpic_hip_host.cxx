@@ -598,6 +598,28 @@ void vpic_simulation::energy_spectrum(species_t *sp, int nex, double dke, float 
     for (int k = 0; k < nbin; k++) spectrum[k] = (float)counts[k];
   }
 }
+void vpic_simulation::distribution(species_t *sp, const vpic_hip_dist_t *d, uint64_t *counts) {
+  if (!sp) ERROR(("Invalid species"));
+  if (!d || !counts) ERROR(("Invalid distribution arguments"));
+  const int id = resident_id(sp->p);
+  if (!engine || id < 0) ERROR(("distribution before the run has started is not supported by this host"));
+  const double origin[3] = {(double)grid->x0, (double)grid->y0, (double)grid->z0};
+  const double cell[3] = {(double)grid->dx, (double)grid->dy, (double)grid->dz};
+  vpic_hip_dist_t local = *d;                               // position axes and ranges: physical units -> cells of this domain
+  for (int a = 0; a < 2; a++) {
+    vpic_hip_dist_axis_t &x = local.axis[a];
+    if (x.coord < VPIC_HIP_COORD_X || x.coord > VPIC_HIP_COORD_Z) continue;
+    x.lo = (x.lo - origin[x.coord]) / cell[x.coord];
+    x.d = x.d / cell[x.coord];
+  }
+  for (int s = 0; s < 4; s++) {
+    vpic_hip_dist_range_t &r = local.sel[s];
+    if (r.coord < VPIC_HIP_COORD_X || r.coord > VPIC_HIP_COORD_Z) continue;
+    r.lo = (r.lo - origin[r.coord]) / cell[r.coord];
+    r.hi = (r.hi - origin[r.coord]) / cell[r.coord];
+  }
+  CK(vpic_hip_species_distribution(engine, id, &local, counts));
+}
 int64_t vpic_simulation::particle_mirror_downloads(void) const { return g_particle_downloads; }
 bool vpic_simulation::resident_energy_f(double *en, const field_t *f) {
   if (!engine || f != field) return false;

@@ -304,6 +304,14 @@ public:
   // (vpic_hip_energy_spectrum): in integers -- the floats written here equal the reference's while every count is
   // below 2^24, where the reference's float counters stop.  Only once the run has started (the engine owns the particles).
   void energy_spectrum(species_t *sp, int nex, double dke, float *bands, int nbin, double log_lo, double dloge, float *spectrum);
+  // A 1-D or 2-D histogram of a species over position, momentum and kinetic energy, of the particles inside up to four
+  // ranges, from the resident state (vpic_hip_species_distribution, include/vpic_hip.h: the descriptor, the arithmetic,
+  // counts[b1 * n0 + b0]).  Unlike the C ABI this takes PHYSICAL units for position axes and ranges (lo, d, hi of an X, Y
+  // or Z coordinate in the units of grid->x0 and grid->dx); they are converted to the cells of this rank's domain as
+  // (lo - grid->x0) / grid->dx and d / grid->dx, in double.  counts[] holds this rank's particles only: every rank bins
+  // against the same physical edges and integer counts add exactly, so a deck on several ranks sums them (as energy.cxx
+  // does with its own).  The particle mirror does not become resident.  Only once the run has started.
+  void distribution(species_t *sp, const vpic_hip_dist_t *d, uint64_t *counts);
   int64_t particle_mirror_downloads(void) const;    // whole-species downloads into the host mirrors so far (diagnostics, tests)
   bool resident_energy_f(double *en, const field_t *f);
 
