@@ -238,9 +238,22 @@ int vpic_hip_set_push_mode(vpic_hip_engine_t *e, int mode);
  * the scheduling or the order messages arrive in.  The reference is reproducible by construction (private accumulators
  * reduced in a fixed order, sf_interface/reduce_accumulators.cxx:37-55); this mode is how the engine gets there.  Particle
  * results are the same in both modes.  Costs the cold decks their in-register run sums (every lane adds for itself).
+ * The hydro moments join the guarantee: accumulate_hydro_p sums every one of a particle's 8 x 14 contributions as a 64-bit
+ * fixed-point integer too (one power-of-two scale per moment and call, from the species' largest macro-particle charge, its
+ * q_m, the cell volume and c: policy.h, moment_scales) and rounds each sum once into the float array, so two runs write the
+ * same hydro dumps bit for bit, whatever order the arrays are in and whichever path summed them; species are added in the
+ * caller's order.  The fixed-point words take 14 x 8 bytes per voxel (1.9 GB at 256^3), allocated by the first
+ * deterministic accumulate_hydro_p and freed with the engine.  A species in tile order is summed tile by tile in LDS without
+ * being reordered; one that the engine would push in tile order is sorted by tile first, as before a deterministic push; any
+ * other species (and every one under VPIC_HIP_MOMENTS_TILED=0) is summed with one global 64-bit atomic per contribution,
+ * which is slow and correct.
  * Limits of the guarantee: rhob (the charge absorbing faces and emitters leave behind, which div-E cleaning reads) is summed
  * with float atomics in both modes; a single deposit beyond 2^14 x 4.2 q_ref (|x * scale| >= 2^51) wraps in the fixed-point
- * conversion -- give q_ref the LARGEST macro-particle charge of the run when charges differ by orders of magnitude. */
+ * conversion -- give q_ref the LARGEST macro-particle charge of the run when charges differ by orders of magnitude.  The
+ * hydro moments convert for every particle with |u| <= 2^12 (2^20 particles of the largest charge at |u| <= 2^7 fit one
+ * sum); a contribution that does not convert (|u| of the order of 2^12 and above: 2^15 for the largest charge) is counted
+ * and never wraps: accumulate_hydro_p then adds nothing, clears its fixed-point words and fails with an error that names the
+ * range (vpic_hip_moments_stats: out[3]).  Float mode has no such limit. */
 int vpic_hip_set_accumulation(vpic_hip_engine_t *e, int mode, double q_ref);
 int vpic_hip_advance_p(vpic_hip_engine_t *e, int sp);       /* species_advance/standard/advance_p.cxx:399-472 (+move_p.c); movers: vpic_hip_species_nm */
 int vpic_hip_sort_p(vpic_hip_engine_t *e, int sp);
@@ -470,7 +483,12 @@ int vpic_hip_compute_rms_div_b_err(vpic_hip_engine_t *e, double *rms);
  * The engine owns one hydro_t array (allocated on first use); a caller accumulates a species into
  * it, synchronises it and reads it back, as dump.cxx:63-70 does per species. */
 int vpic_hip_clear_hydro(vpic_hip_engine_t *e);                      /* sf_interface.c:29-36 */
-int vpic_hip_accumulate_hydro_p(vpic_hip_engine_t *e, int sp);       /* species_advance/standard/hydro_p.c:24-176 (uses the loaded interpolator; float atomics) */
+int vpic_hip_accumulate_hydro_p(vpic_hip_engine_t *e, int sp);       /* species_advance/standard/hydro_p.c:24-176 (uses the loaded interpolator; float atomics, or fixed point: vpic_hip_set_accumulation) */
+/* The last accumulate_hydro_p / accumulate_rho_p call: out[0] live particles summed, out[1] particles added through the LDS
+ * window of their tile (a species in tile order is summed tile by tile and keeps its order), out[2] particles added through
+ * global memory (appended since the sort, drifted out of their tile's window, or a species that is not in tile order), out[3]
+ * contributions outside the fixed-point range of the deterministic mode (vpic_hip_set_accumulation).  Waits for the stream. */
+int vpic_hip_moments_stats(vpic_hip_engine_t *e, int64_t out[4]);
 int vpic_hip_synchronize_hydro(vpic_hip_engine_t *e);                /* sf_interface/hydro.c:28-163: local adjustment + faces shared with itself */
 int vpic_hip_local_adjust_hydro(vpic_hip_engine_t *e);               /* sf_interface/hydro.c:165-200 */
 int vpic_hip_synchronize_hydro_self(vpic_hip_engine_t *e, int axis);

@@ -6,6 +6,7 @@
 #include <vector>
 #include "vpic_hip.h"
 #include "policy.h"
+#include "moments_device.h"
 
 namespace vpichip {
 
@@ -173,6 +174,7 @@ struct Knobs {
   int unload_tiled = 1;            // VPIC_HIP_UNLOAD_TILED: clear_jf + unload_accumulator 0 one thread per voxel through L1 / L2 (rounds 2-3), 2 through LDS tiles, 1 (default) tiles on grids large enough to fill the chip with them
   int field_tiles = 0;             // VPIC_HIP_FIELD_TILES: advance_b / advance_e (one material) 0 (default) one thread per voxel through L1 / L2, 2 through LDS tiles, 1 tiles on grids large enough to fill the chip with them -- measured TWICE as slow (fields.hip)
   bool rho_per_particle = false, hydro_per_particle = false;   // VPIC_HIP_RHO_PER_PARTICLE, VPIC_HIP_HYDRO_PER_PARTICLE
+  bool moments_tiled = true;       // VPIC_HIP_MOMENTS_TILED=0: accumulate_hydro_p / accumulate_rho_p never sum by tile (policy.h: plan_moments; A/B timing)
 };
 Knobs read_knobs();
 
@@ -240,6 +242,11 @@ struct Engine {
   // statistics of the last call, and the pinned buffer {statistics, counters} both come back through
   unsigned long long *dist_counts = nullptr, *dist_stats = nullptr, *dist_host = nullptr; size_t dist_bins = 0;
   int64_t dist_last[4] = {0, 0, 0, 0};
+  // hydro moments and rho summed by tile (moments.hip), allocated by the first call: the fixed-point words of the
+  // deterministic hydro sums (14 per voxel, zero between calls), the statistics of the last call ([4]: tpart is no
+  // partition) and the pinned words they come back through (mom_pending: copied behind the last call, not read yet)
+  unsigned long long *hydro64 = nullptr, *mom_stats = nullptr, *mom_host = nullptr;
+  int64_t mom_last[4] = {0, 0, 0, 0}; bool mom_pending = false;
 
   hipEvent_t step_done[4] = {}; int64_t steps_enqueued = 0;   // vpic_hip_step: the host stays at most two steps ahead of the device
   // profiling
@@ -277,7 +284,8 @@ int k_advance_b(Engine *e, float frac);
 int k_advance_e(Engine *e, int part = 0);   // part: see AdvanceEParams (fields.hip)
 int k_energy_f(Engine *e, double *en6);
 int k_clear_rhof(Engine *e);
-int k_accumulate_rho_p(Engine *e, Species &s);
+int k_accumulate_rho_p(Engine *e, Species &s, bool wants_tile);     // moments.hip; wants_tile: the engine would push the species in tile order
+int k_rho_p_untiled(Engine *e, Species &s, bool by_cell);           // the float paths of a species that is not in tile order
 int k_rho_count(const Engine *e, int dir);
 int k_pack_rho(Engine *e, int dir, float *buf);
 int k_unpack_rho(Engine *e, int dir, const float *buf);
@@ -303,7 +311,10 @@ int k_synchronize_tang_e_norm_b_self(Engine *e, int axis);
 int ensure_hydro(Engine *e);
 int k_dump_gather(Engine *e, int what, int layout, const int32_t *words, int nwords, int sx, int sy, int sz, void *out, size_t out_bytes);
 int k_clear_hydro(Engine *e);
-int k_accumulate_hydro_p(Engine *e, Species &s);
+int k_accumulate_hydro_p(Engine *e, Species &s, bool wants_tile);   // moments.hip
+int k_hydro_p_untiled(Engine *e, Species &s, bool by_cell);
+HydroConsts hydro_consts(const Engine *e, const Species &s);
+int k_moments_stats(Engine *e, int64_t out[4]);
 int k_local_adjust_hydro(Engine *e);
 int k_hydro_count(const Engine *e, int dir);
 int k_pack_hydro(Engine *e, int dir, float *buf);

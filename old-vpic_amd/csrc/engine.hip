@@ -56,6 +56,7 @@ Knobs read_knobs() {
   if (const char *v = getenv("VPIC_HIP_FIELD_TILES")) k.field_tiles = atoi(v);
   k.rho_per_particle = getenv("VPIC_HIP_RHO_PER_PARTICLE") != nullptr;
   k.hydro_per_particle = getenv("VPIC_HIP_HYDRO_PER_PARTICLE") != nullptr;
+  if (const char *v = getenv("VPIC_HIP_MOMENTS_TILED")) k.moments_tiled = atoi(v) != 0;
   return k;
 }
 
@@ -198,6 +199,7 @@ static void destroy(Engine *e) {
   (void)hipFree(e->acc64); (void)hipFree(e->rho64);
   (void)hipFree(e->spec_lin); (void)hipFree(e->spec_bands); (void)hipFree(e->spec_log); (void)hipFree(e->spec_stats); (void)hipHostFree(e->spec_host);
   (void)hipFree(e->dist_counts); (void)hipFree(e->dist_stats); (void)hipHostFree(e->dist_host);
+  (void)hipFree(e->hydro64); (void)hipFree(e->mom_stats); (void)hipHostFree(e->mom_host);
   for (auto &ev : e->ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
   for (auto ev : e->step_done) if (ev) (void)hipEventDestroy(ev);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -728,7 +730,8 @@ int vpic_hip_uncenter_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp
 int vpic_hip_clear_jf(vpic_hip_engine_t *e) { ENGINE(e); return k_clear_jf(e); }
 int vpic_hip_clear_jf_unload_accumulator(vpic_hip_engine_t *e) { ENGINE(e); return k_clear_jf_unload_accumulator(e); }
 int vpic_hip_clear_hydro(vpic_hip_engine_t *e) { ENGINE(e); return k_clear_hydro(e); }
-int vpic_hip_accumulate_hydro_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp); return k_accumulate_hydro_p(e, e->species[sp]); }
+int vpic_hip_accumulate_hydro_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp); return k_accumulate_hydro_p(e, e->species[sp], wants_tile_order(e, e->species[sp])); }
+int vpic_hip_moments_stats(vpic_hip_engine_t *e, int64_t out[4]) { ENGINE(e); if (!out) VH_FAIL("Bad output array"); return k_moments_stats(e, out); }
 int vpic_hip_synchronize_hydro(vpic_hip_engine_t *e) { ENGINE(e); return k_synchronize_hydro_local(e); }
 int vpic_hip_local_adjust_hydro(vpic_hip_engine_t *e) { ENGINE(e); return k_local_adjust_hydro(e); }
 int vpic_hip_synchronize_hydro_self(vpic_hip_engine_t *e, int axis) { ENGINE(e); if (axis < 0 || axis > 2) VH_FAIL("Bad axis"); return k_synchronize_hydro_self(e, axis); }
@@ -759,7 +762,7 @@ int vpic_hip_dump_gather(vpic_hip_engine_t *e, int what, int layout, const int32
   return k_dump_gather(e, what, layout, words, nwords, sx, sy, sz, out, out_bytes);
 }
 int vpic_hip_clear_rhof(vpic_hip_engine_t *e) { ENGINE(e); return k_clear_rhof(e); }
-int vpic_hip_accumulate_rho_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp); return k_accumulate_rho_p(e, e->species[sp]); }
+int vpic_hip_accumulate_rho_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp); return k_accumulate_rho_p(e, e->species[sp], wants_tile_order(e, e->species[sp])); }
 int vpic_hip_synchronize_rho(vpic_hip_engine_t *e) { ENGINE(e); return k_synchronize_rho_local(e); }
 int vpic_hip_local_adjust_rho(vpic_hip_engine_t *e) { ENGINE(e); return k_local_adjust_rho(e); }
 int vpic_hip_synchronize_rho_self(vpic_hip_engine_t *e, int axis) { ENGINE(e); if (axis < 0 || axis > 2) VH_FAIL("Bad axis"); return k_synchronize_rho_self(e, axis); }

@@ -924,36 +924,18 @@ int k_clear_rhof(Engine *e) {
   return 0;
 }
 
-// rho_p.c:43-84: the eight trilinear weights of a particle, added to the nodes of its cell.  The
-// sums are float atomics: same values as the reference's, added in another order.
-// DET (deterministic accumulation, engine.h): the weights are rounded to 64-bit fixed point and summed as integers in rho64;
-// rho_finalize_kernel rounds the sums into rhof.
-template <bool DET>
+// rho_p.c:43-84: the eight trilinear weights of a particle (moments_device.h), added to the nodes of its cell.  The float
+// paths of a species that is NOT in tile order (moments.hip dispatches).  The sums are float atomics: same values as the
+// reference's, added in another order.
 __global__ __launch_bounds__(256)
-void accumulate_rho_p_kernel(float *__restrict__ rhof, ParticlesK p, int np, float r8V, int sy, int sz, double scale) {
+void accumulate_rho_p_kernel(float *__restrict__ rhof, ParticlesK p, int np, float r8V, int sy, int sz) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= np || p.i[idx] < 0) return;          // (a dead slot: engine.h, Species::n_holes)
-  float w0, w1, w2, w3, w4, w5, w6, w7, t;
-  t = p.dx[idx]; w0 = r8V * p.q[idx]; t *= w0; w1 = w0 + t; w0 -= t;
-  t = p.dy[idx]; w3 = 1 + t; w2 = w0 * w3; w3 *= w1; t = 1 - t; w0 *= t; w1 *= t;
-  t = p.dz[idx]; w7 = 1 + t; w4 = w0 * w7; w5 = w1 * w7; w6 = w2 * w7; w7 *= w3;
-  t = 1 - t; w0 *= t; w1 *= t; w2 *= t; w3 *= t;
-  if (DET) {
-    unsigned long long *r = reinterpret_cast<unsigned long long *>(rhof) + p.i[idx];
-    atomicAdd(r, to_fixed(w0, scale)); atomicAdd(r + 1, to_fixed(w1, scale)); atomicAdd(r + sy, to_fixed(w2, scale)); atomicAdd(r + sy + 1, to_fixed(w3, scale));
-    atomicAdd(r + sz, to_fixed(w4, scale)); atomicAdd(r + sz + 1, to_fixed(w5, scale)); atomicAdd(r + sz + sy, to_fixed(w6, scale)); atomicAdd(r + sz + sy + 1, to_fixed(w7, scale));
-    return;
-  }
+  float w[8];
+  node_weights(p.dx[idx], p.dy[idx], p.dz[idx], p.q[idx], r8V, w);
   float *r = rhof + p.i[idx];
-  atomicAdd(r, w0); atomicAdd(r + 1, w1); atomicAdd(r + sy, w2); atomicAdd(r + sy + 1, w3);
-  atomicAdd(r + sz, w4); atomicAdd(r + sz + 1, w5); atomicAdd(r + sz + sy, w6); atomicAdd(r + sz + sy + 1, w7);
-}
-__global__ __launch_bounds__(256)
-void rho_finalize_kernel(float *__restrict__ rhof, unsigned long long *__restrict__ rho64, int nv, double inv_scale) {
-  const int v = blockIdx.x * 256 + threadIdx.x;
-  if (v >= nv) return;
-  const long long s = (long long)rho64[v];
-  if (s) { rhof[v] += (float)((double)s * inv_scale); rho64[v] = 0; }
+  atomicAdd(r, w[0]); atomicAdd(r + 1, w[1]); atomicAdd(r + sy, w[2]); atomicAdd(r + sy + 1, w[3]);
+  atomicAdd(r + sz, w[4]); atomicAdd(r + sz + 1, w[5]); atomicAdd(r + sz + sy, w[6]); atomicAdd(r + sz + sy + 1, w[7]);
 }
 // from a cell-sorted species: one thread per voxel sums the weights of its particles, 8 atomics per
 // occupied cell instead of per particle
@@ -967,44 +949,26 @@ void accumulate_rho_cells_kernel(float *__restrict__ rhof, ParticlesK p, const i
   float s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0, s6 = 0, s7 = 0;
 #pragma unroll 1
   for (int idx = first; idx < last; idx++) {
-    float w0, w1, w2, w3, w4, w5, w6, w7, t;
-    t = p.dx[idx]; w0 = r8V * p.q[idx]; t *= w0; w1 = w0 + t; w0 -= t;
-    t = p.dy[idx]; w3 = 1 + t; w2 = w0 * w3; w3 *= w1; t = 1 - t; w0 *= t; w1 *= t;
-    t = p.dz[idx]; w7 = 1 + t; w4 = w0 * w7; w5 = w1 * w7; w6 = w2 * w7; w7 *= w3;
-    t = 1 - t; w0 *= t; w1 *= t; w2 *= t; w3 *= t;
-    s0 += w0; s1 += w1; s2 += w2; s3 += w3; s4 += w4; s5 += w5; s6 += w6; s7 += w7;
+    float w[8];
+    node_weights(p.dx[idx], p.dy[idx], p.dz[idx], p.q[idx], r8V, w);
+    s0 += w[0]; s1 += w[1]; s2 += w[2]; s3 += w[3]; s4 += w[4]; s5 += w[5]; s6 += w[6]; s7 += w[7];
   }
   float *r = rhof + v;
   atomicAdd(r, s0); atomicAdd(r + 1, s1); atomicAdd(r + sy, s2); atomicAdd(r + sy + 1, s3);
   atomicAdd(r + sz, s4); atomicAdd(r + sz + 1, s5); atomicAdd(r + sz + sy, s6); atomicAdd(r + sz + sy + 1, s7);
 }
-int k_accumulate_rho_p(Engine *e, Species &s) {
-  if (s.np == 0 || s.chargeless) return 0;                                // charge-0 copies add nothing
+int k_rho_p_untiled(Engine *e, Species &s, bool by_cell) {
   const vpic_hip_grid_t &G = e->grid;
   const float r8V = 0.125 * G.rdx * G.rdy * G.rdz;                       // rho_p.c:37
-  if (e->det_acc) {
-    // deterministic accumulation: per-particle fixed-point atomics into rho64, then one rounding into rhof (the species are
-    // added to rhof one after the other, in their fixed order)
-    if (acc_prepare_det(e)) return 1;
-    const size_t nv = (size_t)e->gk.nv;
-    if (!e->rho64) { VH_CHECK(hipMalloc(&e->rho64, sizeof(unsigned long long) * nv)); VH_CHECK(hipMemsetAsync(e->rho64, 0, sizeof(unsigned long long) * nv, e->stream)); }
-    int ex = 0; (void)frexp(8.0 * (double)r8V, &ex);
-    const double scale = ldexp(e->acc_scale, -ex);                       // a weight is at most 8 r8V |q|
-    hipLaunchKernelGGL(accumulate_rho_p_kernel<true>, dim3((unsigned)((s.np + 255) / 256)), dim3(256), 0, e->stream,
-                       reinterpret_cast<float *>(e->rho64), s.p, (int)s.np, r8V, e->gk.sy, e->gk.sz, scale);
-    hipLaunchKernelGGL(rho_finalize_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, e->stream, e->f.c[F_RHOF], e->rho64, (int)nv, 1.0 / scale);
-    VH_CHECK(hipGetLastError());
-    return 0;
-  }
-  if (s.np >= 4 * (int64_t)e->gk.nv && s.nm == 0 && !e->knobs.rho_per_particle) {
+  if (by_cell) {
     if (!s.partition_valid && k_sort_p(e, s)) return 1;
     hipLaunchKernelGGL(accumulate_rho_cells_kernel, dim3((unsigned)((e->gk.nv + 255) / 256)), dim3(256), 0, e->stream,
                        e->f.c[F_RHOF], s.p, s.partition, e->gk.nv, r8V, e->gk.sy, e->gk.sz);
     VH_CHECK(hipGetLastError());
     return 0;
   }
-  hipLaunchKernelGGL(accumulate_rho_p_kernel<false>, dim3((unsigned)((s.np + 255) / 256)), dim3(256), 0, e->stream,
-                     e->f.c[F_RHOF], s.p, (int)s.np, r8V, e->gk.sy, e->gk.sz, 0.0);
+  hipLaunchKernelGGL(accumulate_rho_p_kernel, dim3((unsigned)((s.np + 255) / 256)), dim3(256), 0, e->stream,
+                     e->f.c[F_RHOF], s.p, (int)s.np, r8V, e->gk.sy, e->gk.sz);
   VH_CHECK(hipGetLastError());
   return 0;
 }

@@ -4,6 +4,7 @@
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
+#include <math.h>
 #include <algorithm>
 
 namespace vpichip {
@@ -279,6 +280,70 @@ inline PushPlan plan_push(Policy &s, const PushInputs &in, int n_seg) {
               : !pl.tiled ? (s.wide_window ? PushInstance::row_wide : PushInstance::row_narrow)
               : in.coarse_sorted ? PushInstance::tile_only : pl.fuse ? PushInstance::tile_sort : pl.hist ? PushInstance::tile_hist : PushInstance::tile;
   return pl;
+}
+
+// accumulate_hydro_p / accumulate_rho_p (moments.hip): how the moments of one species are summed.
+//   tiled         one workgroup per tile of a species in tile order (LDS window of the tile's nodes), what was appended
+//                 since the sort one thread per particle; the array is not reordered
+//   per_particle  one thread per particle over the whole array, global atomics (64-bit ones in deterministic mode: slow)
+//   cells         the float path of the reference's order: sorted by voxel first (which costs the tile order), one thread per voxel
+// tpart_ok: tile_valid, tpart[] allocated for this grid, n_sorted within np (whether tpart[] IS a partition is checked on
+// the device; where it is not, everything goes through the per-particle pass); wants_tile: the engine would push the species
+// in tile order (wants_tile_order); per_particle_knob: VPIC_HIP_HYDRO_PER_PARTICLE resp. VPIC_HIP_RHO_PER_PARTICLE;
+// tiled_knob: VPIC_HIP_MOMENTS_TILED (0: the deterministic sums per particle, the float sums as before there was a tile path)
+struct MomentInputs {
+  bool det = false, tile_valid = false, tpart_ok = false, wants_tile = false, per_particle_knob = false, tiled_knob = true;
+  int64_t np = 0, nm = 0, nv = 0;
+};
+enum class MomentPath { tiled, per_particle, cells };
+struct MomentPlan { MomentPath path = MomentPath::per_particle; bool sort_by_tile_first = false; };
+inline MomentPlan plan_moments(const MomentInputs &in) {
+  MomentPlan pl;
+  // the float path of a species that is not in tile order: from a few particles per voxel on, by cell (it sorts by voxel)
+  const MomentPath untiled_float = in.np >= 4 * in.nv && in.nm == 0 && !in.per_particle_knob ? MomentPath::cells : MomentPath::per_particle;
+  if (!in.tiled_knob) { pl.path = in.det ? MomentPath::per_particle : untiled_float; return pl; }
+  if (in.tile_valid && in.tpart_ok && in.nm == 0) { pl.path = MomentPath::tiled; return pl; }
+  if (!in.det) { pl.path = untiled_float; return pl; }
+  // deterministic: a species the engine pushes in tile order is put (back) into it, as before a deterministic push
+  if (in.nm == 0 && in.np > 0 && in.wants_tile) { pl.path = MomentPath::tiled; pl.sort_by_tile_first = true; }
+  return pl;
+}
+
+// Fixed-point scales of the 14 hydro moments in deterministic mode (jx jy jz rho px py pz ke txx tyy tzz tyz tzx txy): one
+// power of two each, chosen per call from the species' largest macro-particle charge q_max, its q_m, r8V = 1 / (8 dV) and c.
+// A particle's weight on a node is at most W = 8 r8V q_max, |v| < c, and its time-centred momentum is |u|, so ONE contribution
+// is at most B(|u|):
+//   jx jy jz   W c                     rho   W
+//   px py pz   W |c / q_m| |u|         ke    W |c / q_m| c |u|   (ke_mc = c u^2 / (gamma + 1) < c |u|)
+//   txx .. txy W |c / q_m| c |u|       (p_i v_j)
+// The off-diagonal stresses tyz tzx txy reach half of their bound only: |u_i u_j| / gamma <= (u_i^2 + u_j^2) / (2 gamma) <
+// |u| / 2 (gamma > |u|).  So the largest contribution at |u| = 1 is R = part B(1), part = 1/2 for those three and 1 elsewhere.
+// With R (1 + 2^-16) = m 2^ex, 1/2 <= m < 1 (frexp), the scale is 2^(36 - ex), the largest power of two the sum below allows:
+// a contribution as large as a particle of weight W at |u| = 1 can make it lands in [2^35, 2^36), strictly below 2^36 by the
+// 2^-16 (the kernel's float arithmetic rounds W, gamma and the products by parts in 2^24 each, a few of them: 2^-16 covers
+// that).  Then
+//   - a unit contribution is at 2^28 or higher (2^35), so half a quantum is 2^-36 of it or less;
+//   - a contribution at |u| <= 2^12 is below 2^36 2^12 = 2^48 < 2^51: it converts (to_fixed needs |x scale| < 2^51; the
+//     kernel counts what does not and the call fails -- from |u| = 2^15 on for weight W, sooner never);
+//   - 2^20 particles of charge q_max at |u| <= 2^7 sum to less than 2^20 2^7 2^36 = 2^63: they fit one signed word.
+// The scale sits at the top of what the sum allows because the small moments of a fast species need it: at |u| = 2^12 along x a
+// tyz contribution is u_y u_z / gamma ~ 2^-15 of the unit, and a node's sum of a couple of hundred of them, signs mixed, is
+// held to 2e-6 of itself by the tests (tests/test_gpu_moments.py: test_range) -- a dozen quanta at this scale.
+// Nothing to scale (a chargeless species, q_m = 0): scale 1, every contribution is 0.
+constexpr int N_HYDRO_MOMENTS = 14;
+struct MomentScales { double scale[N_HYDRO_MOMENTS], bound[N_HYDRO_MOMENTS], part[N_HYDRO_MOMENTS]; };   // bound: B of each moment; part: the share of it a contribution reaches
+inline MomentScales moment_scales(double q_max, double q_m, double r8V, double c) {
+  MomentScales ms;
+  const double W = 8.0 * fabs(r8V) * fabs(q_max), mc_q = q_m != 0 ? fabs(c / q_m) : 0.0;
+  for (int k = 0; k < N_HYDRO_MOMENTS; k++) {
+    const double B = k < 3 ? W * c : k == 3 ? W : k < 7 ? W * mc_q : W * mc_q * c;
+    int ex = 0;
+    ms.bound[k] = B;
+    ms.part[k] = k >= 11 ? 0.5 : 1.0;
+    ms.scale[k] = 1.0;
+    if (B > 0 && B < HUGE_VAL) { (void)frexp(B * ms.part[k] * (1.0 + ldexp(1.0, -16)), &ex); ms.scale[k] = ldexp(1.0, 36 - ex); }
+  }
+  return ms;
 }
 
 }  // namespace vpichip

@@ -1530,65 +1530,24 @@ int k_center_p(Engine *e, Species &s, bool uncenter) {
 }  // namespace vpichip
 
 // ---- hydro moments: species_advance/standard/hydro_p.c:24-176 ----------------
-// The particle is time-centred as in center_p (half E kick, half Boris rotation -- with the
-// reference's double-precision pieces kept: sqrt in double, the series factor in double), then its
-// 14 moments are spread trilinearly over the 8 nodes of its cell.  Sums are float atomics.
+// The float paths of a species that is NOT in tile order (moments.hip dispatches; a particle's numbers: moments_device.h).
+// Sums are float atomics.
 namespace vpichip {
 __global__ __launch_bounds__(256)
-void accumulate_hydro_p_kernel(float *__restrict__ h0, ParticlesK p, const float4 *__restrict__ fi, int np,
-                               float qdt_2mc, float qdt_4mc2, float c, float r8V, float mc_q, int sy, int sz) {
+void accumulate_hydro_p_kernel(float *__restrict__ h0, ParticlesK p, const float4 *__restrict__ fi, int np, HydroConsts hc, int sy, int sz) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= np || p.i[idx] < 0) return;
-  float dx = p.dx[idx], dy = p.dy[idx], dz = p.dz[idx];
   const int ii = p.i[idx];
-  float ux = p.ux[idx], uy = p.uy[idx], uz = p.uz[idx];
-  const float q = p.q[idx];
-  const float4 *f = fi + (size_t)ii * 5;
-  const float4 fe_x = f[0], fe_y = f[1], fe_z = f[2], fb0 = f[3];
-  const float2 fb1 = *reinterpret_cast<const float2 *>(f + 4);
-  float vx, vy, vz, ke_mc, w0, w1, w2, w3, w4, w5, w6, w7;
-  ux += qdt_2mc * ((fe_x.x + dy * fe_x.y) + dz * (fe_x.z + dy * fe_x.w));
-  uy += qdt_2mc * ((fe_y.x + dz * fe_y.y) + dx * (fe_y.z + dz * fe_y.w));
-  uz += qdt_2mc * ((fe_z.x + dx * fe_z.y) + dy * (fe_z.z + dx * fe_z.w));
-  w5 = fb0.x + dx * fb0.y; w6 = fb0.z + dy * fb0.w; w7 = fb1.x + dz * fb1.y;
-  ke_mc = ux * ux + uy * uy + uz * uz;
-  vz = (float)sqrt((double)(1.f + ke_mc));                                   // hydro_p.c:86
-  ke_mc *= c / (vz + 1.f);
-  vz = c / vz;
-  w0 = qdt_4mc2 * vz;
-  w1 = w5 * w5 + w6 * w6 + w7 * w7;
-  w2 = w0 * w0 * w1;
-  w3 = (float)((double)w0 * (1. + (1. / 3.) * (double)w2 * (1. + 0.4 * (double)w2)));   // hydro_p.c:92
-  w4 = w3 / (1.f + w1 * w3 * w3); w4 += w4;
-  w0 = ux + w3 * (uy * w7 - uz * w6);
-  w1 = uy + w3 * (uz * w5 - ux * w7);
-  w2 = uz + w3 * (ux * w6 - uy * w5);
-  ux += w4 * (w1 * w7 - w2 * w6);
-  uy += w4 * (w2 * w5 - w0 * w7);
-  uz += w4 * (w0 * w6 - w1 * w5);
-  vx = ux * vz; vy = uy * vz; vz *= uz;
-  w0 = r8V * q; dx *= w0; w1 = w0 + dx; w0 -= dx;
-  w3 = 1.f + dy; w2 = w0 * w3; w3 *= w1; dy = 1.f - dy; w0 *= dy; w1 *= dy;
-  w7 = 1.f + dz; w4 = w0 * w7; w5 = w1 * w7; w6 = w2 * w7; w7 *= w3;
-  dz = 1.f - dz; w0 *= dz; w1 *= dz; w2 *= dz; w3 *= dz;
-  float *h = h0 + (size_t)ii * 16;
-#define ACCUM_HYDRO(hh, wn) do {                                                                 \
-    float *m = (hh); float w = (wn);                                                             \
-    atomicAdd(m + 0, w * vx); atomicAdd(m + 1, w * vy); atomicAdd(m + 2, w * vz); atomicAdd(m + 3, w); \
-    w *= mc_q; const float ax = w * ux, ay = w * uy, az = w * uz;                                \
-    atomicAdd(m + 4, ax); atomicAdd(m + 5, ay); atomicAdd(m + 6, az); atomicAdd(m + 7, w * ke_mc); \
-    atomicAdd(m + 8, ax * vx); atomicAdd(m + 9, ay * vy); atomicAdd(m + 10, az * vz);             \
-    atomicAdd(m + 11, ay * vz); atomicAdd(m + 12, az * vx); atomicAdd(m + 13, ax * vy);           \
-  } while (0)
-  ACCUM_HYDRO(h, w0);
-  ACCUM_HYDRO(h + 16, w1);
-  ACCUM_HYDRO(h + 16 * (size_t)sy, w2);
-  ACCUM_HYDRO(h + 16 * (size_t)(sy + 1), w3);
-  ACCUM_HYDRO(h + 16 * (size_t)sz, w4);
-  ACCUM_HYDRO(h + 16 * (size_t)(sz + 1), w5);
-  ACCUM_HYDRO(h + 16 * (size_t)(sz + sy), w6);
-  ACCUM_HYDRO(h + 16 * (size_t)(sz + sy + 1), w7);
-#undef ACCUM_HYDRO
+  HydroP P;
+  hydro_particle(p.dx[idx], p.dy[idx], p.dz[idx], p.ux[idx], p.uy[idx], p.uz[idx], p.q[idx], load_interp(fi, ii), hc, P);
+  float *h = h0 + (size_t)ii * HYDRO_STRIDE;
+#pragma unroll
+  for (int n = 0; n < 8; n++) {
+    float *m = h + HYDRO_STRIDE * (size_t)((n & 1) + ((n >> 1) & 1) * sy + (n >> 2) * sz), c[HYDRO_MOMENTS];
+    hydro_node(P, P.w[n], hc.mc_q, c);
+#pragma unroll
+    for (int k = 0; k < HYDRO_MOMENTS; k++) atomicAdd(m + k, c[k]);
+  }
 }
 
 // The same sums from a cell-sorted species: one thread per voxel walks its particles (partition[v] ..
@@ -1597,89 +1556,62 @@ void accumulate_hydro_p_kernel(float *__restrict__ h0, ParticlesK p, const float
 // Every particle contributes the very same 112 products as in the kernel above.
 __global__ __launch_bounds__(256)
 void accumulate_hydro_cells_kernel(float *__restrict__ h0, ParticlesK p, const float4 *__restrict__ fi,
-                                   const int *__restrict__ partition, int nv,
-                                   float qdt_2mc, float qdt_4mc2, float c, float r8V, float mc_q, int sy, int sz) {
+                                   const int *__restrict__ partition, int nv, HydroConsts hc, int sy, int sz) {
   const int ii = blockIdx.x * 256 + threadIdx.x;
   if (ii >= nv) return;
   const int first = partition[ii], last = partition[ii + 1];
   if (first >= last) return;
-  const float4 *f = fi + (size_t)ii * 5;
-  const float4 fe_x = f[0], fe_y = f[1], fe_z = f[2], fb0 = f[3];
-  const float2 fb1 = *reinterpret_cast<const float2 *>(f + 4);
-  float S[8][14];
+  const InterpK f = load_interp(fi, ii);
+  float S[8][HYDRO_MOMENTS];
 #pragma unroll
   for (int n = 0; n < 8; n++)
 #pragma unroll
-    for (int k = 0; k < 14; k++) S[n][k] = 0.f;
+    for (int k = 0; k < HYDRO_MOMENTS; k++) S[n][k] = 0.f;
 #pragma unroll 1
   for (int idx = first; idx < last; idx++) {
-    float dx = p.dx[idx], dy = p.dy[idx], dz = p.dz[idx];
-    float ux = p.ux[idx], uy = p.uy[idx], uz = p.uz[idx];
-    const float q = p.q[idx];
-    float vx, vy, vz, ke_mc, w[8], w5, w6, w7, t0, t1, t2, t3, t4;
-    ux += qdt_2mc * ((fe_x.x + dy * fe_x.y) + dz * (fe_x.z + dy * fe_x.w));
-    uy += qdt_2mc * ((fe_y.x + dz * fe_y.y) + dx * (fe_y.z + dz * fe_y.w));
-    uz += qdt_2mc * ((fe_z.x + dx * fe_z.y) + dy * (fe_z.z + dx * fe_z.w));
-    w5 = fb0.x + dx * fb0.y; w6 = fb0.z + dy * fb0.w; w7 = fb1.x + dz * fb1.y;
-    ke_mc = ux * ux + uy * uy + uz * uz;
-    vz = (float)sqrt((double)(1.f + ke_mc));
-    ke_mc *= c / (vz + 1.f);
-    vz = c / vz;
-    t0 = qdt_4mc2 * vz;
-    t1 = w5 * w5 + w6 * w6 + w7 * w7;
-    t2 = t0 * t0 * t1;
-    t3 = (float)((double)t0 * (1. + (1. / 3.) * (double)t2 * (1. + 0.4 * (double)t2)));
-    t4 = t3 / (1.f + t1 * t3 * t3); t4 += t4;
-    t0 = ux + t3 * (uy * w7 - uz * w6);
-    t1 = uy + t3 * (uz * w5 - ux * w7);
-    t2 = uz + t3 * (ux * w6 - uy * w5);
-    ux += t4 * (t1 * w7 - t2 * w6);
-    uy += t4 * (t2 * w5 - t0 * w7);
-    uz += t4 * (t0 * w6 - t1 * w5);
-    vx = ux * vz; vy = uy * vz; vz *= uz;
-    w[0] = r8V * q; dx *= w[0]; w[1] = w[0] + dx; w[0] -= dx;
-    w[3] = 1.f + dy; w[2] = w[0] * w[3]; w[3] *= w[1]; dy = 1.f - dy; w[0] *= dy; w[1] *= dy;
-    w[7] = 1.f + dz; w[4] = w[0] * w[7]; w[5] = w[1] * w[7]; w[6] = w[2] * w[7]; w[7] *= w[3];
-    dz = 1.f - dz; w[0] *= dz; w[1] *= dz; w[2] *= dz; w[3] *= dz;
+    HydroP P;
+    hydro_particle(p.dx[idx], p.dy[idx], p.dz[idx], p.ux[idx], p.uy[idx], p.uz[idx], p.q[idx], f, hc, P);
 #pragma unroll
     for (int n = 0; n < 8; n++) {
-      float wn = w[n];
-      S[n][0] += wn * vx; S[n][1] += wn * vy; S[n][2] += wn * vz; S[n][3] += wn;
-      wn *= mc_q; const float ax = wn * ux, ay = wn * uy, az = wn * uz;
-      S[n][4] += ax; S[n][5] += ay; S[n][6] += az; S[n][7] += wn * ke_mc;
-      S[n][8] += ax * vx; S[n][9] += ay * vy; S[n][10] += az * vz;
-      S[n][11] += ay * vz; S[n][12] += az * vx; S[n][13] += ax * vy;
+      float c[HYDRO_MOMENTS];
+      hydro_node(P, P.w[n], hc.mc_q, c);
+#pragma unroll
+      for (int k = 0; k < HYDRO_MOMENTS; k++) S[n][k] += c[k];
     }
   }
-  float *h = h0 + (size_t)ii * 16;
+  float *h = h0 + (size_t)ii * HYDRO_STRIDE;
 #pragma unroll
   for (int n = 0; n < 8; n++) {
-    float *m = h + 16 * (size_t)((n & 1) + ((n >> 1) & 1) * sy + (n >> 2) * sz);
+    float *m = h + HYDRO_STRIDE * (size_t)((n & 1) + ((n >> 1) & 1) * sy + (n >> 2) * sz);
 #pragma unroll
-    for (int k = 0; k < 14; k++) atomicAdd(m + k, S[n][k]);
+    for (int k = 0; k < HYDRO_MOMENTS; k++) atomicAdd(m + k, S[n][k]);
   }
 }
 
-int k_accumulate_hydro_p(Engine *e, Species &s) {
-  if (ensure_hydro(e)) return 1;
-  if (s.np == 0) return 0;
+HydroConsts hydro_consts(const Engine *e, const Species &s) {
   const vpic_hip_grid_t &g = e->grid;
-  const float qdt_2mc = 0.5 * s.q_m * g.dt / g.cvac;                          // hydro_p.c:49-53
-  const float qdt_4mc2 = 0.25 * s.q_m * g.dt / (g.cvac * g.cvac);
-  const float r8V = 0.125 * g.rdx * g.rdy * g.rdz;
-  const float mc_q = g.cvac / s.q_m;
-  // from a few particles per voxel on, the per-cell kernel wins by far; it needs the species sorted
-  // (sorting only reorders the array, as the reference's own sort_p does)
-  const bool by_cell = s.np >= 4 * (int64_t)e->gk.nv && s.nm == 0 && !e->knobs.hydro_per_particle;
+  HydroConsts hc;
+  hc.qdt_2mc = 0.5 * s.q_m * g.dt / g.cvac;                                   // hydro_p.c:49-53
+  hc.qdt_4mc2 = 0.25 * s.q_m * g.dt / (g.cvac * g.cvac);
+  hc.c = g.cvac;
+  hc.r8V = 0.125 * g.rdx * g.rdy * g.rdz;
+  hc.mc_q = g.cvac / s.q_m;
+  return hc;
+}
+
+// by_cell: from a few particles per voxel on, the per-cell kernel wins by far; it needs the species sorted by voxel
+// (sorting only reorders the array, as the reference's own sort_p does)
+int k_hydro_p_untiled(Engine *e, Species &s, bool by_cell) {
+  const HydroConsts hc = hydro_consts(e, s);
   if (by_cell) {
     if (!s.partition_valid && k_sort_p(e, s)) return 1;
     hipLaunchKernelGGL(accumulate_hydro_cells_kernel, dim3((unsigned)((e->gk.nv + 255) / 256)), dim3(256), 0, e->stream,
                        reinterpret_cast<float *>(e->hydro), s.p, reinterpret_cast<const float4 *>(e->fi), s.partition, e->gk.nv,
-                       qdt_2mc, qdt_4mc2, g.cvac, r8V, mc_q, e->gk.sy, e->gk.sz);
+                       hc, e->gk.sy, e->gk.sz);
   } else
   hipLaunchKernelGGL(accumulate_hydro_p_kernel, dim3((unsigned)((s.np + 255) / 256)), dim3(256), 0, e->stream,
                      reinterpret_cast<float *>(e->hydro), s.p, reinterpret_cast<const float4 *>(e->fi), (int)s.np,
-                     qdt_2mc, qdt_4mc2, g.cvac, r8V, mc_q, e->gk.sy, e->gk.sz);
+                     hc, e->gk.sy, e->gk.sz);
   VH_CHECK(hipGetLastError());
   return 0;
 }

@@ -392,6 +392,13 @@ class Engine:
     def accumulate_hydro_p(self, sp):
         self._ck(self._l.vpic_hip_accumulate_hydro_p(self._h, sp))
 
+    def moments_stats(self):
+        """(live particles summed, added through an LDS window, added through global memory, contributions out of the
+        fixed-point range) of the last accumulate_hydro_p / accumulate_rho_p call (include/vpic_hip.h)."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._l.vpic_hip_moments_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
     def synchronize_hydro(self):
         self._ck(self._l.vpic_hip_synchronize_hydro(self._h))
 
