@@ -370,6 +370,57 @@ int vpic_hip_species_distribution(vpic_hip_engine_t *e, int sp, const vpic_hip_d
  *     added in global memory, the lanes of a wavefront that share a bin adding once together, and out[3] == out[2].
  * Misses cost time, never the result. */
 int vpic_hip_species_distribution_stats(vpic_hip_engine_t *e, int64_t out[4]);
+
+/* ---- selected particles of a species: those inside up to four ranges and with the tags asked for, gathered into dense
+ * arrays where the particles are, so that only they come to the host (csrc/select.hip) ----
+ * Live particles: 0 <= i < nv; dead slots (i = -1) are skipped, particles appended since the last sort are included.
+ * Coordinates and ranges are exactly those of vpic_hip_species_distribution above: IEEE double, every operation
+ *   rounded once, unfused; a particle is inside a range when lo <= c < hi, so a NaN is never kept.
+ * Tags: `tag` is the particle's FIRST tag (vpic_particle_t::tag).  A species whose tag arrays were never allocated
+ *   (no non-zero tag was ever uploaded) behaves as if every tag were 0, and the call allocates nothing for it.
+ *     VPIC_HIP_SELECT_TAG_RANGE  keep when tag_lo <= tag < tag_hi
+ *     VPIC_HIP_SELECT_TAG_EVERY  keep when ((tag % tag_every) + tag_every) % tag_every == tag_phase, % as in C: the
+ *                                non-negative remainder, for negative tags too
+ * Combination: a particle is kept when every one of the n_sel ranges and every enabled tag condition holds (no range
+ *   and no flag: every live particle).
+ * Order: record k is the k-th kept particle in increasing array index (stable), index[k] that array index (it counts
+ *   dead slots: below the extent that vpic_hip_species_capacity reports).  Two calls on an unchanged species return
+ *   identical bytes.
+ * p[k]: the particle as vpic_hip_species_get_particles would return it, all 48 bytes, both tags.
+ * fields[6k .. 6k+5]: ex, ey, ez, cbx, cby, cbz at the particle, from the interpolator AS IT IS LOADED at the call
+ *   (the caller runs vpic_hip_load_interpolator when it wants the current fields).  The arithmetic is that of
+ *   advance_p.cxx:74-82 without the qdt_2mc factor, in float, every operation rounded once, unfused; f is the
+ *   interpolator of the particle's voxel:
+ *     ex  = (f.ex + dy*f.dexdy) + dz*(f.dexdz + dy*f.d2exdydz)
+ *     ey  = (f.ey + dz*f.deydz) + dx*(f.deydx + dz*f.d2eydzdx)
+ *     ez  = (f.ez + dx*f.dezdx) + dy*(f.dezdy + dx*f.d2ezdxdy)
+ *     cbx = f.cbx + dx*f.dcbxdx,  cby = f.cby + dy*f.dcbydy,  cbz = f.cbz + dz*f.dcbzdz
+ * Outputs and cap: p, fields and index are host arrays of cap records each (48 bytes, six floats, one int64); any of
+ *   them may be NULL, and that part is then neither computed nor copied.  *count is ALWAYS the number of kept
+ *   particles; only the first min(*count, cap) records are written, and the call still returns 0: the caller compares
+ *   *count with cap.
+ * The species is read and nothing about it changes: no compaction (its dead slots stay), its order, tile partition,
+ *   sort bookkeeping and pending histogram stay, no host mirror becomes resident.
+ * Fails (non-zero, vpic_hip_last_error) on a bad sp, a NULL s or count, n_sel outside 0..4, an unknown coordinate,
+ * unknown flag bits, (TAG_EVERY) tag_every < 1 or tag_phase outside [0, tag_every), cap < 0, or a device allocation
+ * that fails (the device arrays belong to the engine and grow on demand: 1 bit per particle, 12 bytes per 2048
+ * particles, and 48 + 24 + 8 bytes per record written for the parts asked for). */
+enum { VPIC_HIP_SELECT_TAG_RANGE = 1, VPIC_HIP_SELECT_TAG_EVERY = 2 };
+typedef struct {
+  int32_t n_sel, flags;                 /* 0 to 4 ranges; VPIC_HIP_SELECT_* bits */
+  vpic_hip_dist_range_t sel[4];         /* as in vpic_hip_dist_t: keep when lo <= c < hi for every range */
+  int64_t tag_lo, tag_hi;               /* TAG_RANGE: keep when tag_lo <= tag < tag_hi */
+  int64_t tag_every, tag_phase;         /* TAG_EVERY: keep when ((tag % every) + every) % every == phase */
+} vpic_hip_select_t;
+VPIC_HIP_STATIC_ASSERT(sizeof(vpic_hip_select_t) == 136, "vpic_hip_select_t layout");
+/* the count alone: the marking pass and the scan, nothing is written */
+int vpic_hip_species_select_count(vpic_hip_engine_t *e, int sp, const vpic_hip_select_t *s, int64_t *count);
+int vpic_hip_species_select(vpic_hip_engine_t *e, int sp, const vpic_hip_select_t *s, int64_t cap,
+                            vpic_particle_t *p, float *fields, int64_t *index, int64_t *count);
+/* The last call of either: out[0] live particles seen, out[1] particles kept, out[2] records written (min(kept, cap);
+ * 0 for select_count and when every output array was NULL), out[3] the chunks (of 2048 particles) the array was cut
+ * into. */
+int vpic_hip_species_select_stats(vpic_hip_engine_t *e, int64_t out[4]);
 int vpic_hip_center_p(vpic_hip_engine_t *e, int sp);        /* species_advance/standard/center_p.cxx: u(-1/2) -> u(0) */
 int vpic_hip_uncenter_p(vpic_hip_engine_t *e, int sp);      /* species_advance/standard/uncenter_p.cxx:154-177: u(0) -> u(-1/2) */
 int vpic_hip_clear_jf(vpic_hip_engine_t *e);                /* field_advance/standard/sfa.c:188-211 */

@@ -2,9 +2,8 @@
 // the particles inside a region (vpic_hip_species_distribution; include/vpic_hip.h states the arithmetic).  One
 // streaming pass over those SoA arrays the descriptor names (x-ux: i, dx, ux, 12 B per particle).  Every counter is
 // an integer: the result does not depend on the order of the array nor on which kernel instance pushed it.
-#include "engine.h"
+#include "dist_coords.h"
 #include <algorithm>
-#include <math.h>
 
 namespace vpichip {
 
@@ -22,8 +21,6 @@ struct DistK {
   int n0, n1;                                  // bins per axis (n1 = 1 for one axis)
   int pos_axis, win, n_other;                  // DIST_WINDOW: which axis slides, bins of it per window, bins of the other axis
 };
-
-constexpr unsigned NEED_POS = 7u, NEED_KE = 3u << VPIC_HIP_COORD_KE;
 
 // DIST_WINDOW on a species in tile order: which particles a wavefront takes.  All tiles with the same tile index along
 // the position axis (a "column") touch the same few bins of it, so a wavefront that takes `group` tiles of ONE column
@@ -46,20 +43,6 @@ void dist_check_tiles_kernel(const int *__restrict__ tpart, int ntiles, long lon
   if (j >= ntiles) return;
   const long long b0 = tpart[(size_t)j * TILE_CELLS], b1 = j + 1 < ntiles ? (long long)tpart[(size_t)(j + 1) * TILE_CELLS] : n_sorted;
   if (b0 < 0 || b0 > b1 || b1 > n_sorted || (j == 0 && b0 != 0)) atomicOr(bad, 1u);
-}
-
-struct DistCoords { double x, y, z, ux, uy, uz, ke, log_ke; };
-
-// a select chain: the coordinate number is uniform, the values stay in registers
-__device__ __forceinline__ double dist_coord(const DistCoords &v, int coord) {
-  return coord == VPIC_HIP_COORD_X ? v.x : coord == VPIC_HIP_COORD_Y ? v.y : coord == VPIC_HIP_COORD_Z ? v.z
-       : coord == VPIC_HIP_COORD_UX ? v.ux : coord == VPIC_HIP_COORD_UY ? v.uy : coord == VPIC_HIP_COORD_UZ ? v.uz
-       : coord == VPIC_HIP_COORD_KE ? v.ke : v.log_ke;
-}
-
-__device__ __forceinline__ bool dist_in_range(const DistCoords &v, const vpic_hip_dist_range_t &r) {
-  const double c = dist_coord(v, r.coord);
-  return c >= r.lo && c < r.hi;
 }
 
 // the lanes for which `on` holds add 1 to word[a]; those that share the first such lane's word add once, together
@@ -104,25 +87,6 @@ __device__ __forceinline__ void flush_dist_window(unsigned *win, int base, const
     }
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-}
-
-// what one lane reads of one particle (only the arrays the descriptor needs)
-struct DistRaw { int voxel; float dx, dy, dz, ux, uy, uz; };
-
-// The loads of a pass do not wait for one another (a dead slot's other words are read and not used), and the main loop
-// asks for the next pass's before it works on this one's.
-__device__ __forceinline__ DistRaw dist_load(const ParticlesK &p, long long idx, long long end, unsigned need) {
-  DistRaw r{-1, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (idx < end) {
-    r.voxel = p.i[idx];
-    if (need & 1u) r.dx = p.dx[idx];
-    if (need & 2u) r.dy = p.dy[idx];
-    if (need & 4u) r.dz = p.dz[idx];
-    if (need & (NEED_KE | 1u << VPIC_HIP_COORD_UX)) r.ux = p.ux[idx];
-    if (need & (NEED_KE | 1u << VPIC_HIP_COORD_UY)) r.uy = p.uy[idx];
-    if (need & (NEED_KE | 1u << VPIC_HIP_COORD_UZ)) r.uz = p.uz[idx];
-  }
-  return r;
 }
 
 // One pass over the species; every wavefront takes a contiguous chunk of the array.
@@ -197,29 +161,14 @@ void species_distribution_kernel(ParticlesK p, long long np, long long chunk, Di
     DistCoords v{};
     int cell_pos = 0;                                                        // DIST_WINDOW: the particle's cell along the position axis, from 0
     if (live) {
-      if (k.need & NEED_POS) {
-        const int cz = (int)(__umulhi((unsigned)voxel, t.mul_sz) >> t.sh_sz), rem = voxel - cz * t.sz;
-        const int cy = (int)(__umulhi((unsigned)rem, t.mul_sy) >> t.sh_sy), cx = rem - cy * t.sy;
-        if (k.need & 1u) v.x = (double)(cx - 1) + ((double)r.dx + 1.0) * 0.5;
-        if (k.need & 2u) v.y = (double)(cy - 1) + ((double)r.dy + 1.0) * 0.5;
-        if (k.need & 4u) v.z = (double)(cz - 1) + ((double)r.dz + 1.0) * 0.5;
-        if (PATH == DIST_WINDOW) {
-          const int c = k.pos_axis == 0 ? k.d.axis[0].coord : k.d.axis[1].coord;
-          cell_pos = (c == VPIC_HIP_COORD_X ? cx : c == VPIC_HIP_COORD_Y ? cy : cz) - 1;
-        }
-      }
-      v.ux = (double)r.ux; v.uy = (double)r.uy; v.uz = (double)r.uz;
-      if (k.need & NEED_KE) {
-        // as spectrum.hip: summed from the left
-        v.ke = sqrt(((1.0 + v.ux * v.ux) + v.uy * v.uy) + v.uz * v.uz) - 1.0;
-        if (k.need & 1u << VPIC_HIP_COORD_LOG10_KE) v.log_ke = log10(v.ke);
+      int cx = 0, cy = 0, cz = 0;
+      v = dist_coords(r, k.need, t, cx, cy, cz);                             // (dist_coords.h)
+      if (PATH == DIST_WINDOW) {
+        const int c = k.pos_axis == 0 ? k.d.axis[0].coord : k.d.axis[1].coord;
+        cell_pos = (c == VPIC_HIP_COORD_X ? cx : c == VPIC_HIP_COORD_Y ? cy : cz) - 1;
       }
     }
-    bool kept = live;
-    if (k.d.n_sel > 0) kept = kept && dist_in_range(v, k.d.sel[0]);
-    if (k.d.n_sel > 1) kept = kept && dist_in_range(v, k.d.sel[1]);
-    if (k.d.n_sel > 2) kept = kept && dist_in_range(v, k.d.sel[2]);
-    if (k.d.n_sel > 3) kept = kept && dist_in_range(v, k.d.sel[3]);
+    const bool kept = live && dist_in_ranges(v, k.d.sel, k.d.n_sel);
     n_kept += __popcll(__ballot(kept));
     bool counted = kept;
     int b0 = 0, b1 = 0;

@@ -247,6 +247,13 @@ struct Engine {
   // partition) and the pinned words they come back through (mom_pending: copied behind the last call, not read yet)
   unsigned long long *hydro64 = nullptr, *mom_stats = nullptr, *mom_host = nullptr;
   int64_t mom_last[4] = {0, 0, 0, 0}; bool mom_pending = false;
+  // selected particles (select.hip), allocated by the first call and grown on demand: one keep bit per particle, the
+  // kept count and the 64-bit offset of every chunk, {live particles seen, kept} and the pinned words they come back
+  // through, the device output arrays (records, six floats per record, indices), and the statistics of the last call
+  unsigned long long *sel_mask = nullptr, *sel_offsets = nullptr, *sel_stats = nullptr, *sel_host = nullptr; unsigned *sel_counts = nullptr;
+  size_t sel_mask_n = 0, sel_offsets_n = 0, sel_counts_n = 0;
+  vpic_particle_t *sel_p = nullptr; float *sel_f = nullptr; int64_t *sel_i = nullptr; size_t sel_p_n = 0, sel_f_n = 0, sel_i_n = 0;
+  int64_t sel_last[4] = {0, 0, 0, 0};
 
   hipEvent_t step_done[4] = {}; int64_t steps_enqueued = 0;   // vpic_hip_step: the host stays at most two steps ahead of the device
   // profiling
@@ -333,6 +340,8 @@ int k_center_p(Engine *e, Species &s, bool uncenter);
 int k_energy_spectrum(Engine *e, Species &s, const vpic_hip_spectrum_t &sp);   // into Engine::spec_lin / spec_log; waits for the stream
 int k_energy_bands(Engine *e, int n_lin);                                        // Engine::spec_lin -> spec_bands
 int k_species_distribution(Engine *e, Species &s, const vpic_hip_dist_t &d);     // into Engine::dist_counts / dist_host; waits for the stream
+// select.hip: launches 1 and 2 (count_only: no masks), and launch 3 into Engine::sel_p / sel_f / sel_i where asked for; waits for the stream
+int k_species_select(Engine *e, Species &s, const vpic_hip_select_t &d, int64_t cap, bool want_p, bool want_f, bool want_i, bool count_only);
 int k_sort_p(Engine *e, Species &s, bool tile_order = false, bool may_fuse = false);   // may_fuse: the caller pushes the species next (see Species::fuse_pending)
 int k_sort_scan(Engine *e, const int *counts, int *starts, int n1);                  // exclusive scan of counts[0..n1) into starts[] and Engine::sort_next[]
 int k_sort_check(Engine *e, Species &s, const int *starts, int n1);                    // every cursor ended where the next key begins? (PW_SORT_CHECK; the next push fails loudly otherwise)

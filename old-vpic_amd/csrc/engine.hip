@@ -200,6 +200,8 @@ static void destroy(Engine *e) {
   (void)hipFree(e->spec_lin); (void)hipFree(e->spec_bands); (void)hipFree(e->spec_log); (void)hipFree(e->spec_stats); (void)hipHostFree(e->spec_host);
   (void)hipFree(e->dist_counts); (void)hipFree(e->dist_stats); (void)hipHostFree(e->dist_host);
   (void)hipFree(e->hydro64); (void)hipFree(e->mom_stats); (void)hipHostFree(e->mom_host);
+  (void)hipFree(e->sel_mask); (void)hipFree(e->sel_offsets); (void)hipFree(e->sel_counts); (void)hipFree(e->sel_stats); (void)hipHostFree(e->sel_host);
+  (void)hipFree(e->sel_p); (void)hipFree(e->sel_f); (void)hipFree(e->sel_i);
   for (auto &ev : e->ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
   for (auto ev : e->step_done) if (ev) (void)hipEventDestroy(ev);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -723,6 +725,45 @@ int vpic_hip_species_distribution(vpic_hip_engine_t *e, int sp, const vpic_hip_d
 int vpic_hip_species_distribution_stats(vpic_hip_engine_t *e, int64_t out[4]) {
   ENGINE(e); if (!out) VH_FAIL("Bad output");
   for (int j = 0; j < 4; j++) out[j] = e->dist_last[j];
+  return 0;
+}
+static int check_select(const vpic_hip_select_t *s) {
+  if (!s) VH_FAIL("Bad select descriptor");
+  if (s->n_sel < 0 || s->n_sel > 4) VH_FAIL("select: %d ranges (0 to 4)", s->n_sel);
+  for (int r = 0; r < s->n_sel; r++)
+    if (s->sel[r].coord < VPIC_HIP_COORD_X || s->sel[r].coord > VPIC_HIP_COORD_LOG10_KE) VH_FAIL("select: unknown coordinate %d of range %d", s->sel[r].coord, r);
+  if (s->flags & ~(VPIC_HIP_SELECT_TAG_RANGE | VPIC_HIP_SELECT_TAG_EVERY)) VH_FAIL("select: unknown flag bits 0x%x", (unsigned)s->flags);
+  if (s->flags & VPIC_HIP_SELECT_TAG_EVERY) {
+    if (s->tag_every < 1) VH_FAIL("select: tag_every %lld (at least 1)", (long long)s->tag_every);
+    if (s->tag_phase < 0 || s->tag_phase >= s->tag_every) VH_FAIL("select: tag_phase %lld outside [0, %lld)", (long long)s->tag_phase, (long long)s->tag_every);
+  }
+  return 0;
+}
+int vpic_hip_species_select_count(vpic_hip_engine_t *e, int sp, const vpic_hip_select_t *s, int64_t *count) {
+  ENGINE(e); SPECIES(e, sp);
+  if (check_select(s)) return 1;
+  if (!count) VH_FAIL("Bad count");
+  if (k_species_select(e, e->species[sp], *s, 0, false, false, false, true)) return 1;
+  *count = e->sel_last[1];
+  return 0;
+}
+int vpic_hip_species_select(vpic_hip_engine_t *e, int sp, const vpic_hip_select_t *s, int64_t cap,
+                            vpic_particle_t *p, float *fields, int64_t *index, int64_t *count) {
+  ENGINE(e); SPECIES(e, sp);
+  if (check_select(s)) return 1;
+  if (!count) VH_FAIL("Bad count");
+  if (cap < 0) VH_FAIL("select: cap %lld is negative", (long long)cap);
+  if (k_species_select(e, e->species[sp], *s, cap, p != nullptr, fields != nullptr, index != nullptr, false)) return 1;
+  *count = e->sel_last[1];
+  const size_t n = (size_t)e->sel_last[2];                  // records written: min(count, cap), 0 when no array was given
+  if (n && p && copy_out(e, p, e->sel_p, sizeof(*p) * n)) return 1;
+  if (n && fields && copy_out(e, fields, e->sel_f, sizeof(float) * 6 * n)) return 1;
+  if (n && index && copy_out(e, index, e->sel_i, sizeof(int64_t) * n)) return 1;
+  return 0;
+}
+int vpic_hip_species_select_stats(vpic_hip_engine_t *e, int64_t out[4]) {
+  ENGINE(e); if (!out) VH_FAIL("Bad output");
+  for (int j = 0; j < 4; j++) out[j] = e->sel_last[j];
   return 0;
 }
 int vpic_hip_center_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp); return k_center_p(e, e->species[sp], false); }

@@ -7,6 +7,7 @@ in the reference's own array-of-struct layouts (layout.py).  Everything computes
 through libvpic_hip.so; errors raise VpicHipError (the reference would print and exit(1),
 src/util/util_base.h:213-219).
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -57,6 +58,23 @@ DIST_COORDS = {"x": 0, "y": 1, "z": 2, "ux": 3, "uy": 4, "uz": 5, "ke": 6, "log1
 DIST_MAX_BINS, DIST_LDS_BINS = 1 << 22, 8192                                                   # VPIC_HIP_DIST_*
 
 
+class SelectDesc(C.Structure):
+    """vpic_hip_select_t (include/vpic_hip.h)"""
+    _fields_ = [("n_sel", C.c_int32), ("flags", C.c_int32), ("sel", DistRange * 4),
+                ("tag_lo", C.c_int64), ("tag_hi", C.c_int64), ("tag_every", C.c_int64), ("tag_phase", C.c_int64)]
+
+
+assert C.sizeof(SelectDesc) == 136
+SELECT_TAG_RANGE, SELECT_TAG_EVERY = 1, 2                                                      # VPIC_HIP_SELECT_*
+SelectResult = collections.namedtuple("SelectResult", "count particles fields index")
+
+
+def _set_ranges(desc, select):
+    """the (coord, lo, hi) ranges of `select`, coordinates by name, into desc.sel (vpic_hip_dist_range_t[4])"""
+    for k, (coord, lo, hi) in enumerate(select):
+        desc.sel[k] = DistRange(DIST_COORDS[coord], 0, float(lo), float(hi))
+
+
 def dist_desc(axes, select=()):
     """vpic_hip_dist_t of one or two (coord, lo, d, n) axes and up to four (coord, lo, hi) ranges, coordinates by name."""
     axes, select = list(axes), list(select)
@@ -65,8 +83,23 @@ def dist_desc(axes, select=()):
     d = DistDesc(len(axes), len(select))
     for k, (coord, lo, width, n) in enumerate(axes):
         d.axis[k] = DistAxis(DIST_COORDS[coord], int(n), float(lo), float(width))
-    for k, (coord, lo, hi) in enumerate(select):
-        d.sel[k] = DistRange(DIST_COORDS[coord], 0, float(lo), float(hi))
+    _set_ranges(d, select)
+    return d
+
+
+def select_desc(select=(), tag_range=None, tag_every=None):
+    """vpic_hip_select_t of up to four (coord, lo, hi) ranges, tag_range = (lo, hi) and tag_every = (every, phase)."""
+    select = list(select)
+    if len(select) > 4:
+        raise ValueError("select: at most four ranges")
+    d = SelectDesc(len(select), 0)
+    _set_ranges(d, select)
+    if tag_range is not None:
+        d.flags |= SELECT_TAG_RANGE
+        d.tag_lo, d.tag_hi = int(tag_range[0]), int(tag_range[1])
+    if tag_every is not None:
+        d.flags |= SELECT_TAG_EVERY
+        d.tag_every, d.tag_phase = int(tag_every[0]), int(tag_every[1])
     return d
 
 
@@ -377,6 +410,41 @@ class Engine:
         """(live particles seen, kept by the selection, counted, added through global memory) of the last distribution call."""
         out = (C.c_int64 * 4)()
         self._ck(self._l.vpic_hip_species_distribution_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
+    # ---- selected particles (include/vpic_hip.h: vpic_hip_species_select) ----
+    def select_count(self, sp, select=(), tag_range=None, tag_every=None):
+        """how many live particles of the species lie inside every (coord, lo, hi) range of `select` and have the tags
+        asked for: tag_range = (lo, hi) keeps lo <= tag < hi, tag_every = (every, phase) keeps tag % every == phase."""
+        d = select_desc(select, tag_range, tag_every)
+        n = C.c_int64()
+        self._ck(self._l.vpic_hip_species_select_count(self._h, int(sp), C.byref(d), C.byref(n)))
+        return n.value
+
+    def select(self, sp, select=(), tag_range=None, tag_every=None, cap=None, fields=False, index=False):
+        """SelectResult(count, particles, fields, index) of those particles, in the order of the species' array:
+        particles particle_t[n]; fields float32[n, 6], (ex, ey, ez, cbx, cby, cbz) at the particle from the interpolator
+        as it is loaded, or None; index int64[n], the particle's place in the array, or None.  n = count, or
+        min(count, cap) when a cap is given (count is the number kept either way); without one the particles are counted
+        first and the arrays sized exactly."""
+        d = select_desc(select, tag_range, tag_every)
+        if cap is None:
+            cap = self.select_count(sp, select, tag_range, tag_every)
+        cap = int(cap)
+        room = max(cap, 0)
+        p = np.zeros(room, L.particle_t)
+        f = np.zeros((room, 6), np.float32) if fields else None
+        i = np.zeros(room, np.int64) if index else None
+        n = C.c_int64()
+        self._ck(self._l.vpic_hip_species_select(self._h, int(sp), C.byref(d), cap, _ptr(p), _ptr(f) if fields else None,
+                                                 _ptr(i) if index else None, C.byref(n)))
+        m = min(n.value, room)
+        return SelectResult(n.value, p[:m], f[:m] if fields else None, i[:m] if index else None)
+
+    def select_stats(self):
+        """(live particles seen, kept, records written, chunks the array was cut into) of the last select / select_count call."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._l.vpic_hip_species_select_stats(self._h, out))
         return tuple(int(v) for v in out)
 
     def center_p(self, sp):

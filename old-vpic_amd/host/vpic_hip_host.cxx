@@ -620,6 +620,24 @@ void vpic_simulation::distribution(species_t *sp, const vpic_hip_dist_t *d, uint
   }
   CK(vpic_hip_species_distribution(engine, id, &local, counts));
 }
+int64_t vpic_simulation::select_particles(species_t *sp, const vpic_hip_select_t *s, int64_t cap, particle_t *p, float *fields, int64_t *index) {
+  if (!sp) ERROR(("Invalid species"));
+  if (!s) ERROR(("Invalid select arguments"));
+  const int id = resident_id(sp->p);
+  if (!engine || id < 0) ERROR(("select_particles before the run has started is not supported by this host"));
+  const double origin[3] = {(double)grid->x0, (double)grid->y0, (double)grid->z0};
+  const double cell[3] = {(double)grid->dx, (double)grid->dy, (double)grid->dz};
+  vpic_hip_select_t local = *s;                             // position ranges: physical units -> cells of this domain, as distribution()
+  for (int k = 0; k < 4; k++) {
+    vpic_hip_dist_range_t &r = local.sel[k];
+    if (r.coord < VPIC_HIP_COORD_X || r.coord > VPIC_HIP_COORD_Z) continue;
+    r.lo = (r.lo - origin[r.coord]) / cell[r.coord];
+    r.hi = (r.hi - origin[r.coord]) / cell[r.coord];
+  }
+  int64_t count = 0;
+  CK(vpic_hip_species_select(engine, id, &local, cap, p, fields, index, &count));
+  return count;
+}
 int64_t vpic_simulation::particle_mirror_downloads(void) const { return g_particle_downloads; }
 bool vpic_simulation::resident_energy_f(double *en, const field_t *f) {
   if (!engine || f != field) return false;

@@ -312,6 +312,15 @@ public:
   // against the same physical edges and integer counts add exactly, so a deck on several ranks sums them (as energy.cxx
   // does with its own).  The particle mirror does not become resident.  Only once the run has started.
   void distribution(species_t *sp, const vpic_hip_dist_t *d, uint64_t *counts);
+  // The particles of a species inside up to four ranges and with the tags asked for, from the resident state, in place of
+  // a loop over sp->p that tests every particle (vpic_hip_species_select, include/vpic_hip.h: the descriptor, the order,
+  // the arithmetic of the fields).  Returns how many particles are kept; the first min(that, cap) of them are written, in
+  // the order of the species' array: p[k] the particle, fields[6k .. 6k+5] ex, ey, ez, cbx, cby, cbz at it from the
+  // interpolator as it stands on the device, index[k] its place in the device's array (not in sp->p once that has been
+  // downloaded: a download drops dead slots).  Any of the three may be NULL.  Position ranges are in PHYSICAL units,
+  // converted as distribution() converts them.  This rank's particles only.  The particle mirror does not become resident.
+  // Only once the run has started.
+  int64_t select_particles(species_t *sp, const vpic_hip_select_t *s, int64_t cap, particle_t *p, float *fields, int64_t *index);
   int64_t particle_mirror_downloads(void) const;    // whole-species downloads into the host mirrors so far (diagnostics, tests)
   bool resident_energy_f(double *en, const field_t *f);
 
