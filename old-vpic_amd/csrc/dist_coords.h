@@ -58,10 +58,7 @@ __device__ __forceinline__ DistRaw dist_load(const ParticlesK &p, long long idx,
 __device__ __forceinline__ DistCoords dist_coords(const DistRaw &r, unsigned need, const TileK &t, int &cx, int &cy, int &cz) {
   DistCoords v{};
   if (need & NEED_POS) {
-    cz = (int)(__umulhi((unsigned)r.voxel, t.mul_sz) >> t.sh_sz);
-    const int rem = r.voxel - cz * t.sz;
-    cy = (int)(__umulhi((unsigned)rem, t.mul_sy) >> t.sh_sy);
-    cx = rem - cy * t.sy;
+    voxel_cell(r.voxel, t, cx, cy, cz);
     if (need & 1u) v.x = (double)(cx - 1) + ((double)r.dx + 1.0) * 0.5;
     if (need & 2u) v.y = (double)(cy - 1) + ((double)r.dy + 1.0) * 0.5;
     if (need & 4u) v.z = (double)(cz - 1) + ((double)r.dz + 1.0) * 0.5;

@@ -141,18 +141,75 @@ struct TileK {
 };
 TileK make_tile_k(const GridK &g);
 
+// the cell (cx, cy, cz) of a voxel, ghost layers included (interior cells from 1): two divisions by the voxel strides
+__device__ __forceinline__ void voxel_cell(int voxel, const TileK &t, int &cx, int &cy, int &cz) {
+  cz = (int)(__umulhi((unsigned)voxel, t.mul_sz) >> t.sh_sz);
+  const int rem = voxel - cz * t.sz;
+  cy = (int)(__umulhi((unsigned)rem, t.mul_sy) >> t.sh_sy);
+  cx = rem - cy * t.sy;
+}
+
 // sort key of a voxel: its own index (the reference's order, sort_p.c:48-58), or tile-major (TILE): tile by tile,
 // cell by cell within the tile
 template <bool TILE>
 __device__ __forceinline__ int sort_key(int voxel, const TileK &t) {
   if (!TILE) return voxel;
-  const int cz = (int)(__umulhi((unsigned)voxel, t.mul_sz) >> t.sh_sz), rem = voxel - cz * t.sz;
-  const int cy = (int)(__umulhi((unsigned)rem, t.mul_sy) >> t.sh_sy), cx = rem - cy * t.sy;
+  int cx, cy, cz;
+  voxel_cell(voxel, t, cx, cy, cz);
   // particles live in interior voxels (1..n); an index in a ghost layer (the reference's sort_p takes any voxel) is
   // counted with the nearest interior cell's tile instead of indexing outside the tables
   const int x = min(max(cx - 1, 0), 4 * t.ntx - 1), y = min(max(cy - 1, 0), 4 * t.nty - 1), z = min(max(cz - 1, 0), 4 * t.ntz - 1);
   const int tile = ((z >> 2) * t.nty + (y >> 2)) * t.ntx + (x >> 2);
   return tile * TILE_CELLS + ((z & 3) << 4 | (y & 3) << 2 | (x & 3));
+}
+
+// ---- pieces the passes over one species share (spectrum.hip, distribution.hip, moments.hip, select.hip) ---------------------
+// the lanes for which `on` holds add 1 to word[a]; those that share the first such lane's word add once, together
+// (a cold beam puts a whole wavefront in one word; more rounds of this, word by word, measured slower than letting the
+// others add for themselves)
+template <typename T>
+__device__ __forceinline__ void add_together(T *word, int a, bool on, int lane) {
+  const unsigned long long any = __ballot(on);
+  if (!any) return;
+  const int lead = __ffsll((long long)any) - 1;
+  const int a0 = __builtin_amdgcn_readlane(a, lead);
+  const unsigned long long same = __ballot(on && a == a0);
+  if (on) {
+    if (a != a0) atomicAdd(word + a, (T)1);
+    else if (lane == lead) atomicAdd(word + a, (T)__popcll(same));
+  }
+}
+
+// THE SLIDING WINDOW of a wavefront: `n_slots` consecutive positions (sort keys, bins of a position axis) x `stride` counters
+// in LDS, [slot * stride + offset], from position `base` on.  Per pass of 64 particles the lanes whose position is inside the
+// window add there; if some are not, the window is flushed (flush(base): the caller adds it to global memory and clears it)
+// and moved to place(left), `left` being the lanes still waiting, and they try again, twice at the most; when more than
+// half the wavefront still misses after that, the window stays where it is for the next WINDOW_BACKOFF passes (an array in
+// no order: the window cannot help, and flushing it every pass would only cost).  A lane with pos < 0 never asks for a
+// slide.  Returns whether this lane is still waiting: the caller adds it to global memory and counts a miss.
+constexpr int WINDOW_BACKOFF = 16;
+struct SlideWindow {
+  int base = 0, backoff = 0;
+  bool placed = false;               // the window has been given a place
+};
+template <typename Place, typename Flush>
+__device__ __forceinline__ bool window_add(SlideWindow &w, unsigned *win, int n_slots, int stride, int pos, int offset, bool pending, int lane,
+                                           Place place, Flush flush) {
+  for (int round = 0; round < 3; round++) {
+    if (round > 0) {
+      const unsigned long long left = __ballot(pending && pos >= 0);
+      if (!left) break;
+      if (w.backoff > 0) { w.backoff--; break; }
+      if (w.placed) flush(w.base);
+      w.base = place(left);
+      w.placed = true;
+    }
+    const bool hit = w.placed && pending && pos >= w.base && pos < w.base + n_slots;
+    add_together(win, (pos - w.base) * stride + offset, hit, lane);
+    if (hit) pending = false;
+    if (round == 2 && __popcll(__ballot(pending)) > 32) w.backoff = WINDOW_BACKOFF;
+  }
+  return pending;
 }
 
 // Environment knobs (experiments and tests; none is needed in production), read ONCE when the engine is created
@@ -177,6 +234,42 @@ struct Knobs {
   bool moments_tiled = true;       // VPIC_HIP_MOMENTS_TILED=0: accumulate_hydro_p / accumulate_rho_p never sum by tile (policy.h: plan_moments; A/B timing)
 };
 Knobs read_knobs();
+
+// "grow a scratch buffer": at least `want` elements of device memory, or (grow_pinned) of pinned host memory; what it held is dropped
+template <typename T, bool PINNED = false>
+inline int grow(T *&buf, size_t &have, size_t want) {
+  if (want <= have) return 0;
+  (void)(PINNED ? hipHostFree(buf) : hipFree(buf)); buf = nullptr; have = 0;
+  VH_CHECK(PINNED ? hipHostMalloc((void **)&buf, want * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)&buf, want * sizeof(T)));
+  have = want;
+  return 0;
+}
+template <typename T> inline int grow_pinned(T *&buf, size_t &have, size_t want) { return grow<T, true>(buf, have, want); }
+
+// The statistics of a diagnostic's last call: up to four 64-bit words its kernels add to on the device, the pinned words they
+// come back through, and what was read.  Word STATS_BAD_PARTITION is k_check_tile_partition's flag (never read back).
+constexpr int STATS_WORDS = 4, STATS_BAD_PARTITION = 4;
+struct DiagStats {
+  unsigned long long *dev = nullptr, *host = nullptr;
+  int64_t last[STATS_WORDS] = {0, 0, 0, 0};
+  bool pending = false;              // a caller that defers its read (moments.hip) says so here
+  // before a call's kernels: allocated by the first call, zeroed on the stream
+  int begin(hipStream_t stream) {
+    if (!dev) VH_CHECK(hipMalloc((void **)&dev, (STATS_WORDS + 1) * sizeof(unsigned long long)));
+    if (!host) VH_CHECK(hipHostMalloc((void **)&host, STATS_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
+    VH_CHECK(hipMemsetAsync(dev, 0, (STATS_WORDS + 1) * sizeof(unsigned long long), stream));
+    return 0;
+  }
+  // behind them: copied, the stream waited for, last[] filled
+  int read(hipStream_t stream) {
+    VH_CHECK(hipMemcpyAsync(host, dev, STATS_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    VH_CHECK(hipStreamSynchronize(stream));
+    for (int j = 0; j < STATS_WORDS; j++) last[j] = (int64_t)host[j];
+    pending = false;
+    return 0;
+  }
+  unsigned *bad_partition() const { return reinterpret_cast<unsigned *>(dev + STATS_BAD_PARTITION); }
+};
 
 struct Engine {
   int device = 0;
@@ -203,7 +296,7 @@ struct Engine {
   unsigned long long *acc64 = nullptr, *rho64 = nullptr;
 
   // scratch
-  void *stage = nullptr; size_t stage_bytes = 0;       // AoS <-> SoA staging
+  char *stage = nullptr; size_t stage_bytes = 0;       // AoS <-> SoA staging
   int *counters = nullptr;                             // small device ints (mover count, ...)
   void *acc_block = nullptr;                           // allocation behind `acc`
   bool time_kernels = false;                           // adaptive sorting in use: time every sort_p / advance_p with events
@@ -234,26 +327,26 @@ struct Engine {
   int *tile_list[2] = {nullptr, nullptr}; int tile_list_n[2] = {0, 0};
 
   // energy spectra (spectrum.hip), allocated by the first call: the linear bands' counters and their normalised form
-  // (n_lin x nv), the log bins, {particles counted, window misses} of the last call, and the pinned words both are read through
-  unsigned *spec_lin = nullptr; float *spec_bands = nullptr; size_t spec_lin_words = 0;
-  unsigned long long *spec_log = nullptr, *spec_stats = nullptr, *spec_host = nullptr;
-  int64_t spec_last[2] = {0, 0};
-  // phase-space distributions (distribution.hip), allocated by the first call and grown on demand: the counters, the four
-  // statistics of the last call, and the pinned buffer {statistics, counters} both come back through
-  unsigned long long *dist_counts = nullptr, *dist_stats = nullptr, *dist_host = nullptr; size_t dist_bins = 0;
-  int64_t dist_last[4] = {0, 0, 0, 0};
+  // (n_lin x nv), the log bins and the pinned words they come back through; statistics {particles counted, window misses}
+  unsigned *spec_lin = nullptr; float *spec_bands = nullptr; size_t spec_lin_words = 0;   // (spec_bands is as long as spec_lin)
+  unsigned long long *spec_log = nullptr, *spec_log_host = nullptr;                          // VPIC_HIP_SPECTRUM_MAX_LOG words each
+  DiagStats spec_stats;
+  // phase-space distributions (distribution.hip), allocated by the first call and grown on demand: the counters and the
+  // pinned buffer they come back through; statistics {seen, kept, counted, misses}
+  unsigned long long *dist_counts = nullptr, *dist_host = nullptr; size_t dist_bins = 0, dist_host_bins = 0;
+  DiagStats dist_stats;
   // hydro moments and rho summed by tile (moments.hip), allocated by the first call: the fixed-point words of the
-  // deterministic hydro sums (14 per voxel, zero between calls), the statistics of the last call ([4]: tpart is no
-  // partition) and the pinned words they come back through (mom_pending: copied behind the last call, not read yet)
-  unsigned long long *hydro64 = nullptr, *mom_stats = nullptr, *mom_host = nullptr;
-  int64_t mom_last[4] = {0, 0, 0, 0}; bool mom_pending = false;
+  // deterministic hydro sums (14 per voxel, zero between calls); statistics {live, through LDS, through global memory, out
+  // of range} (mom_stats.pending: the last call's are still on the device, not read yet)
+  unsigned long long *hydro64 = nullptr;
+  DiagStats mom_stats;
   // selected particles (select.hip), allocated by the first call and grown on demand: one keep bit per particle, the
-  // kept count and the 64-bit offset of every chunk, {live particles seen, kept} and the pinned words they come back
-  // through, the device output arrays (records, six floats per record, indices), and the statistics of the last call
-  unsigned long long *sel_mask = nullptr, *sel_offsets = nullptr, *sel_stats = nullptr, *sel_host = nullptr; unsigned *sel_counts = nullptr;
+  // kept count and the 64-bit offset of every chunk, the device output arrays (records, six floats per record, indices);
+  // statistics {live particles seen, kept, written, chunks}
+  unsigned long long *sel_mask = nullptr, *sel_offsets = nullptr; unsigned *sel_counts = nullptr;
   size_t sel_mask_n = 0, sel_offsets_n = 0, sel_counts_n = 0;
   vpic_particle_t *sel_p = nullptr; float *sel_f = nullptr; int64_t *sel_i = nullptr; size_t sel_p_n = 0, sel_f_n = 0, sel_i_n = 0;
-  int64_t sel_last[4] = {0, 0, 0, 0};
+  DiagStats sel_stats;
 
   hipEvent_t step_done[4] = {}; int64_t steps_enqueued = 0;   // vpic_hip_step: the host stays at most two steps ahead of the device
   // profiling
@@ -322,6 +415,11 @@ int k_accumulate_hydro_p(Engine *e, Species &s, bool wants_tile);   // moments.h
 int k_hydro_p_untiled(Engine *e, Species &s, bool by_cell);
 HydroConsts hydro_consts(const Engine *e, const Species &s);
 int k_moments_stats(Engine *e, int64_t out[4]);
+// tpart[] of a species in tile order: usable at all (host), and a partition of [0, n_sorted) (device: *bad is set where not; moments.hip)
+int k_check_tile_partition(Engine *e, const Species &s, unsigned *bad);
+inline bool tile_partition_usable(const Species &s, const TileK &t) {
+  return s.tile_valid && s.tpart && s.tpart_count >= (int64_t)t.ntiles * TILE_CELLS + 1 && s.n_sorted >= 0 && s.n_sorted <= s.np;
+}
 int k_local_adjust_hydro(Engine *e);
 int k_hydro_count(const Engine *e, int dir);
 int k_pack_hydro(Engine *e, int dir, float *buf);
@@ -337,7 +435,7 @@ int k_particles_to_aos(Engine *e, Species &s, vpic_particle_t *host, int64_t cap
 int k_load_maxwellian(Engine *e, Species &s, int ppc, unsigned seed, float q, float ux, float uy, float uz, float vth);
 int k_energy_p(Engine *e, Species &s, double *energy);
 int k_center_p(Engine *e, Species &s, bool uncenter);
-int k_energy_spectrum(Engine *e, Species &s, const vpic_hip_spectrum_t &sp);   // into Engine::spec_lin / spec_log; waits for the stream
+int k_energy_spectrum(Engine *e, Species &s, const vpic_hip_spectrum_t &sp);   // into Engine::spec_lin / spec_log / spec_log_host; waits for the stream
 int k_energy_bands(Engine *e, int n_lin);                                        // Engine::spec_lin -> spec_bands
 int k_species_distribution(Engine *e, Species &s, const vpic_hip_dist_t &d);     // into Engine::dist_counts / dist_host; waits for the stream
 // select.hip: launches 1 and 2 (count_only: no masks), and launch 3 into Engine::sel_p / sel_f / sel_i where asked for; waits for the stream

@@ -28,14 +28,7 @@ static vpic_hip_host_access_fn g_host_access = nullptr;
 void host_will_read(const void *p, size_t bytes) { if (g_host_access && p && bytes) g_host_access(p, bytes, 0); }
 void host_will_write(void *p, size_t bytes) { if (g_host_access && p && bytes) g_host_access(p, bytes, 1); }
 
-int ensure_stage(Engine *e, size_t bytes) {
-  if (bytes <= e->stage_bytes) return 0;
-  if (e->stage) (void)hipFree(e->stage);
-  e->stage = nullptr; e->stage_bytes = 0;
-  VH_CHECK(hipMalloc(&e->stage, bytes));
-  e->stage_bytes = bytes;
-  return 0;
-}
+int ensure_stage(Engine *e, size_t bytes) { return grow(e->stage, e->stage_bytes, bytes); }
 
 Knobs read_knobs() {
   Knobs k;
@@ -197,11 +190,11 @@ static void destroy(Engine *e) {
   (void)hipFree(e->sp_table_dev); (void)hipHostFree(e->sp_table_host); (void)hipFree(e->xmsg_dev); (void)hipHostFree(e->xmsg_host);
   (void)hipFree(e->retry_buf); (void)hipFree(e->tile_list[0]); (void)hipFree(e->tile_list[1]);
   (void)hipFree(e->acc64); (void)hipFree(e->rho64);
-  (void)hipFree(e->spec_lin); (void)hipFree(e->spec_bands); (void)hipFree(e->spec_log); (void)hipFree(e->spec_stats); (void)hipHostFree(e->spec_host);
-  (void)hipFree(e->dist_counts); (void)hipFree(e->dist_stats); (void)hipHostFree(e->dist_host);
-  (void)hipFree(e->hydro64); (void)hipFree(e->mom_stats); (void)hipHostFree(e->mom_host);
-  (void)hipFree(e->sel_mask); (void)hipFree(e->sel_offsets); (void)hipFree(e->sel_counts); (void)hipFree(e->sel_stats); (void)hipHostFree(e->sel_host);
+  (void)hipFree(e->spec_lin); (void)hipFree(e->spec_bands); (void)hipFree(e->spec_log); (void)hipHostFree(e->spec_log_host);
+  (void)hipFree(e->dist_counts); (void)hipHostFree(e->dist_host); (void)hipFree(e->hydro64);
+  (void)hipFree(e->sel_mask); (void)hipFree(e->sel_offsets); (void)hipFree(e->sel_counts);
   (void)hipFree(e->sel_p); (void)hipFree(e->sel_f); (void)hipFree(e->sel_i);
+  for (DiagStats *st : {&e->spec_stats, &e->dist_stats, &e->mom_stats, &e->sel_stats}) { (void)hipFree(st->dev); (void)hipHostFree(st->host); }
   for (auto &ev : e->ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
   for (auto ev : e->step_done) if (ev) (void)hipEventDestroy(ev);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -658,6 +651,17 @@ int vpic_hip_energy_p(vpic_hip_engine_t *e, int sp, double *energy) {
   if (!energy) VH_FAIL("Bad energy");
   return k_energy_p(e, e->species[sp], energy);
 }
+// the ranges of a distribution or a selection (`what` names the caller in the message)
+static int check_range_count(const char *what, int n_sel) {
+  if (n_sel < 0 || n_sel > 4) VH_FAIL("%s: %d ranges (0 to 4)", what, n_sel);
+  return 0;
+}
+static int check_ranges(const char *what, const vpic_hip_dist_range_t *sel, int n_sel) {
+  if (check_range_count(what, n_sel)) return 1;
+  for (int r = 0; r < n_sel; r++)
+    if (sel[r].coord < VPIC_HIP_COORD_X || sel[r].coord > VPIC_HIP_COORD_LOG10_KE) VH_FAIL("%s: unknown coordinate %d of range %d", what, sel[r].coord, r);
+  return 0;
+}
 static int check_spectrum(const vpic_hip_spectrum_t *s, bool need_lin) {
   if (!s) VH_FAIL("Bad spectrum parameters");
   if (s->n_lin < 0 || s->n_log < 0) VH_FAIL("energy spectrum: negative count (n_lin %d, n_log %d)", s->n_lin, s->n_log);
@@ -678,7 +682,7 @@ int vpic_hip_energy_spectrum(vpic_hip_engine_t *e, int sp, const vpic_hip_spectr
   host_will_write(log_counts, sizeof(uint64_t) * (size_t)want.n_log);
   if (k_energy_spectrum(e, e->species[sp], want)) return 1;
   if (lin_bytes) VH_CHECK(hipMemcpy(lin_counts, e->spec_lin, lin_bytes, hipMemcpyDeviceToHost));
-  if (want.n_log) memcpy(log_counts, e->spec_host + 2, sizeof(uint64_t) * (size_t)want.n_log);
+  if (want.n_log) memcpy(log_counts, e->spec_log_host, sizeof(uint64_t) * (size_t)want.n_log);
   return 0;
 }
 int vpic_hip_energy_bands(vpic_hip_engine_t *e, int sp, const vpic_hip_spectrum_t *s, float *bands) {
@@ -694,17 +698,19 @@ int vpic_hip_energy_bands(vpic_hip_engine_t *e, int sp, const vpic_hip_spectrum_
   VH_CHECK(hipStreamSynchronize(e->stream));
   return 0;
 }
-int vpic_hip_energy_spectrum_stats(vpic_hip_engine_t *e, int64_t out[2]) {
-  ENGINE(e); if (!out) VH_FAIL("Bad output");
-  out[0] = e->spec_last[0]; out[1] = e->spec_last[1];
+// the first n statistics of a diagnostic's last call
+static int copy_stats(const DiagStats &st, int64_t *out, int n) {
+  if (!out) VH_FAIL("Bad output");
+  for (int j = 0; j < n; j++) out[j] = st.last[j];
   return 0;
 }
+int vpic_hip_energy_spectrum_stats(vpic_hip_engine_t *e, int64_t out[2]) { ENGINE(e); return copy_stats(e->spec_stats, out, 2); }
 int vpic_hip_species_distribution(vpic_hip_engine_t *e, int sp, const vpic_hip_dist_t *d, uint64_t *counts) {
   ENGINE(e); SPECIES(e, sp);
   if (!d) VH_FAIL("Bad distribution descriptor");
   if (!counts) VH_FAIL("Bad counts array");
   if (d->n_axes != 1 && d->n_axes != 2) VH_FAIL("distribution: %d axes (1 or 2)", d->n_axes);
-  if (d->n_sel < 0 || d->n_sel > 4) VH_FAIL("distribution: %d ranges (0 to 4)", d->n_sel);
+  if (check_range_count("distribution", d->n_sel)) return 1;   // (the order of the checks: count, axes, the ranges' coordinates)
   long long bins = 1;
   for (int a = 0; a < d->n_axes; a++) {
     const vpic_hip_dist_axis_t &x = d->axis[a];
@@ -713,25 +719,18 @@ int vpic_hip_species_distribution(vpic_hip_engine_t *e, int sp, const vpic_hip_d
     if (!(x.d > 0) || !std::isfinite(x.d)) VH_FAIL("distribution: bin width %g of axis %d", x.d, a);
     bins *= x.n;                                            // (at most 2^62)
   }
-  for (int s = 0; s < d->n_sel; s++)
-    if (d->sel[s].coord < VPIC_HIP_COORD_X || d->sel[s].coord > VPIC_HIP_COORD_LOG10_KE) VH_FAIL("distribution: unknown coordinate %d of range %d", d->sel[s].coord, s);
+  if (check_ranges("distribution", d->sel, d->n_sel)) return 1;
   if (bins > VPIC_HIP_DIST_MAX_BINS) VH_FAIL("distribution: %lld bins above the cap of %d", bins, VPIC_HIP_DIST_MAX_BINS);
   const size_t bytes = sizeof(uint64_t) * (size_t)bins;
   host_will_write(counts, bytes);
   if (k_species_distribution(e, e->species[sp], *d)) return 1;
-  memcpy(counts, e->dist_host + 4, bytes);
+  memcpy(counts, e->dist_host, bytes);
   return 0;
 }
-int vpic_hip_species_distribution_stats(vpic_hip_engine_t *e, int64_t out[4]) {
-  ENGINE(e); if (!out) VH_FAIL("Bad output");
-  for (int j = 0; j < 4; j++) out[j] = e->dist_last[j];
-  return 0;
-}
+int vpic_hip_species_distribution_stats(vpic_hip_engine_t *e, int64_t out[4]) { ENGINE(e); return copy_stats(e->dist_stats, out, 4); }
 static int check_select(const vpic_hip_select_t *s) {
   if (!s) VH_FAIL("Bad select descriptor");
-  if (s->n_sel < 0 || s->n_sel > 4) VH_FAIL("select: %d ranges (0 to 4)", s->n_sel);
-  for (int r = 0; r < s->n_sel; r++)
-    if (s->sel[r].coord < VPIC_HIP_COORD_X || s->sel[r].coord > VPIC_HIP_COORD_LOG10_KE) VH_FAIL("select: unknown coordinate %d of range %d", s->sel[r].coord, r);
+  if (check_ranges("select", s->sel, s->n_sel)) return 1;
   if (s->flags & ~(VPIC_HIP_SELECT_TAG_RANGE | VPIC_HIP_SELECT_TAG_EVERY)) VH_FAIL("select: unknown flag bits 0x%x", (unsigned)s->flags);
   if (s->flags & VPIC_HIP_SELECT_TAG_EVERY) {
     if (s->tag_every < 1) VH_FAIL("select: tag_every %lld (at least 1)", (long long)s->tag_every);
@@ -744,7 +743,7 @@ int vpic_hip_species_select_count(vpic_hip_engine_t *e, int sp, const vpic_hip_s
   if (check_select(s)) return 1;
   if (!count) VH_FAIL("Bad count");
   if (k_species_select(e, e->species[sp], *s, 0, false, false, false, true)) return 1;
-  *count = e->sel_last[1];
+  *count = e->sel_stats.last[1];
   return 0;
 }
 int vpic_hip_species_select(vpic_hip_engine_t *e, int sp, const vpic_hip_select_t *s, int64_t cap,
@@ -754,18 +753,14 @@ int vpic_hip_species_select(vpic_hip_engine_t *e, int sp, const vpic_hip_select_
   if (!count) VH_FAIL("Bad count");
   if (cap < 0) VH_FAIL("select: cap %lld is negative", (long long)cap);
   if (k_species_select(e, e->species[sp], *s, cap, p != nullptr, fields != nullptr, index != nullptr, false)) return 1;
-  *count = e->sel_last[1];
-  const size_t n = (size_t)e->sel_last[2];                  // records written: min(count, cap), 0 when no array was given
+  *count = e->sel_stats.last[1];
+  const size_t n = (size_t)e->sel_stats.last[2];                  // records written: min(count, cap), 0 when no array was given
   if (n && p && copy_out(e, p, e->sel_p, sizeof(*p) * n)) return 1;
   if (n && fields && copy_out(e, fields, e->sel_f, sizeof(float) * 6 * n)) return 1;
   if (n && index && copy_out(e, index, e->sel_i, sizeof(int64_t) * n)) return 1;
   return 0;
 }
-int vpic_hip_species_select_stats(vpic_hip_engine_t *e, int64_t out[4]) {
-  ENGINE(e); if (!out) VH_FAIL("Bad output");
-  for (int j = 0; j < 4; j++) out[j] = e->sel_last[j];
-  return 0;
-}
+int vpic_hip_species_select_stats(vpic_hip_engine_t *e, int64_t out[4]) { ENGINE(e); return copy_stats(e->sel_stats, out, 4); }
 int vpic_hip_center_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp); return k_center_p(e, e->species[sp], false); }
 int vpic_hip_uncenter_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp); return k_center_p(e, e->species[sp], true); }
 int vpic_hip_clear_jf(vpic_hip_engine_t *e) { ENGINE(e); return k_clear_jf(e); }

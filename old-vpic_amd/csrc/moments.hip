@@ -7,7 +7,8 @@
 //               in 64-bit words, 19.2 KB in floats); a particle whose cell is inside adds there, any other (particles drift out
 //               of their tile between sorts) straight to global memory; at the end the non-zero words go to global memory.
 //   tail pass   one thread per particle over [n_sorted, np) -- or over the whole array, for a species that is not in tile
-//               order and may not be sorted, and where tpart[] turns out not to be a partition -- with global atomics.
+//               order and may not be sorted, and where tpart[] turns out not to be a partition (k_check_tile_partition,
+//               defined here and shared with distribution.hip) -- with global atomics.
 //   finalize    (fixed point) hydro[v].m += (float)(sum / scale_m), one rounding per word and call, and the word is zeroed.
 // The array is not reordered and nothing the push or the next sort relies on is touched.
 #include "engine.h"
@@ -33,12 +34,20 @@ struct MomK {
   unsigned long long *stats;                             // live particles, through LDS, through global memory, contributions out of range
 };
 
+// tpart[] is a partition of [0, n_sorted): non-decreasing from 0, within n_sorted (*bad is set where it is not)
 __global__ __launch_bounds__(256)
-void moments_check_tiles_kernel(const int *__restrict__ tpart, int ntiles, long long n_sorted, unsigned *__restrict__ bad) {
+void check_tile_partition_kernel(const int *__restrict__ tpart, int ntiles, long long n_sorted, unsigned *__restrict__ bad) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= ntiles) return;
   const long long b0 = tpart[(size_t)j * TILE_CELLS], b1 = j + 1 < ntiles ? (long long)tpart[(size_t)(j + 1) * TILE_CELLS] : n_sorted;
   if (b0 < 0 || b0 > b1 || b1 > n_sorted || (j == 0 && b0 != 0)) atomicOr(bad, 1u);
+}
+int k_check_tile_partition(Engine *e, const Species &s, unsigned *bad) {
+  const int ntiles = make_tile_k(e->gk).ntiles;
+  hipLaunchKernelGGL(check_tile_partition_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, e->stream, (const int *)s.tpart, ntiles,
+                     (long long)s.n_sorted, bad);
+  VH_CHECK(hipGetLastError());
+  return 0;
 }
 
 // one contribution: a float add, or rounded to fixed point and added as an integer (what does not convert is counted, not added)
@@ -69,8 +78,8 @@ __device__ __forceinline__ void moments_of_particle(const MomK &K, ACC *__restri
   bool inside = false;
   int slot0 = 0;
   if (WINDOW) {
-    const int cz = (int)(__umulhi((unsigned)voxel, K.t.mul_sz) >> K.t.sh_sz), rem = voxel - cz * K.t.sz;
-    const int cy = (int)(__umulhi((unsigned)rem, K.t.mul_sy) >> K.t.sh_sy), cx = rem - cy * K.t.sy;
+    int cx, cy, cz;
+    voxel_cell(voxel, K.t, cx, cy, cz);
     const unsigned lx = (unsigned)(cx - bx), ly = (unsigned)(cy - by), lz = (unsigned)(cz - bz);
     inside = lx < (unsigned)(MOM_WX - 1) && ly < (unsigned)(MOM_WX - 1) && lz < (unsigned)(MOM_WX - 1);
     slot0 = (int)(lx + MOM_WX * (ly + MOM_WX * lz));
@@ -164,26 +173,19 @@ void moments_finalize_kernel(float *__restrict__ out, unsigned long long *__rest
   }
 }
 
-static int ensure_moments(Engine *e) {
-  if (!e->mom_stats) VH_CHECK(hipMalloc((void **)&e->mom_stats, 5 * sizeof(unsigned long long)));   // ([4]: MomK::bad)
-  if (!e->mom_host) VH_CHECK(hipHostMalloc((void **)&e->mom_host, 4 * sizeof(unsigned long long), hipHostMallocDefault));
-  return 0;
-}
-
 // the kernels of one call: `tiled`: tile pass + tail pass; otherwise the per-particle pass over the whole array
 template <int NM, typename ACC>
 static int launch_moments(Engine *e, Species &s, MomK &K, ACC *out, bool tiled) {
-  VH_CHECK(hipMemsetAsync(e->mom_stats, 0, 5 * sizeof(unsigned long long), e->stream));
+  if (e->mom_stats.begin(e->stream)) return 1;
   K.p = s.p; K.fi = reinterpret_cast<const float4 *>(e->fi); K.np = s.np;
   K.sy = e->gk.sy; K.sz = e->gk.sz; K.nv_safe = e->gk.nv - e->gk.sz - e->gk.sy - 1;
   K.t = make_tile_k(e->gk);
-  K.stats = e->mom_stats;
+  K.stats = e->mom_stats.dev;
   K.tpart = nullptr; K.bad = nullptr; K.n_sorted = 0;
   if (s.np > 0) {
     if (tiled) {
-      K.tpart = s.tpart; K.bad = reinterpret_cast<const unsigned *>(e->mom_stats + 4); K.n_sorted = s.n_sorted;
-      hipLaunchKernelGGL(moments_check_tiles_kernel, dim3((K.t.ntiles + 255) / 256), dim3(256), 0, e->stream, s.tpart, K.t.ntiles,
-                         (long long)s.n_sorted, reinterpret_cast<unsigned *>(e->mom_stats + 4));
+      K.tpart = s.tpart; K.bad = e->mom_stats.bad_partition(); K.n_sorted = s.n_sorted;
+      if (k_check_tile_partition(e, s, e->mom_stats.bad_partition())) return 1;
       hipLaunchKernelGGL((moments_tile_kernel<NM, ACC>), dim3((unsigned)K.t.ntiles), dim3(256), 0, e->stream, K, out);
     }
     // (a tpart[] that is no partition sends the whole array through this pass: sized for that)
@@ -191,35 +193,28 @@ static int launch_moments(Engine *e, Species &s, MomK &K, ACC *out, bool tiled) 
     hipLaunchKernelGGL((moments_tail_kernel<NM, ACC>), dim3(nb), dim3(256), 0, e->stream, K, out);
     VH_CHECK(hipGetLastError());
   }
-  VH_CHECK(hipMemcpyAsync(e->mom_host, e->mom_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-  e->mom_pending = true;
+  e->mom_stats.pending = true;                             // (read when somebody asks: read_moments_stats)
   return 0;
 }
 
-static int read_moments_stats(Engine *e) {
-  if (e->mom_pending) {
-    VH_CHECK(hipStreamSynchronize(e->stream));
-    for (int j = 0; j < 4; j++) e->mom_last[j] = (int64_t)e->mom_host[j];
-    e->mom_pending = false;
-  }
-  return 0;
-}
+static int read_moments_stats(Engine *e) { return e->mom_stats.pending ? e->mom_stats.read(e->stream) : 0; }
 int k_moments_stats(Engine *e, int64_t out[4]) {
   if (read_moments_stats(e)) return 1;
-  for (int j = 0; j < 4; j++) out[j] = e->mom_last[j];
+  for (int j = 0; j < 4; j++) out[j] = e->mom_stats.last[j];
   return 0;
 }
 // a call that took one of the float paths of push.hip / fields.hip: every live particle through global memory
 static void book_untiled(Engine *e, const Species &s) {
-  e->mom_pending = false;
-  e->mom_last[0] = e->mom_last[2] = s.np - s.n_holes; e->mom_last[1] = e->mom_last[3] = 0;
+  int64_t *last = e->mom_stats.last;
+  e->mom_stats.pending = false;
+  last[0] = last[2] = s.np - s.n_holes; last[1] = last[3] = 0;
 }
 
 static MomentPlan plan_for(Engine *e, Species &s, bool wants_tile, bool per_particle_knob) {
   const TileK tk = make_tile_k(e->gk);
   MomentInputs in;
   in.det = e->det_acc; in.tile_valid = s.tile_valid; in.wants_tile = wants_tile;
-  in.tpart_ok = s.tile_valid && s.tpart && s.tpart_count >= (int64_t)tk.ntiles * TILE_CELLS + 1 && s.n_sorted >= 0 && s.n_sorted <= s.np;
+  in.tpart_ok = tile_partition_usable(s, tk);
   in.per_particle_knob = per_particle_knob; in.tiled_knob = e->knobs.moments_tiled;
   in.np = s.np; in.nm = s.nm; in.nv = e->gk.nv;
   return plan_moments(in);
@@ -232,7 +227,6 @@ int k_accumulate_hydro_p(Engine *e, Species &s, bool wants_tile) {
     book_untiled(e, s);
     return s.np == 0 ? 0 : k_hydro_p_untiled(e, s, pl.path == MomentPath::cells);
   }
-  if (ensure_moments(e)) return 1;
   if (pl.sort_by_tile_first && k_sort_p(e, s, true)) return 1;
   MomK K{};
   K.h = hydro_consts(e, s);
@@ -247,10 +241,10 @@ int k_accumulate_hydro_p(Engine *e, Species &s, bool wants_tile) {
   for (int k = 0; k < HYDRO_MOMENTS; k++) { K.scale[k] = ms.scale[k]; inv.s[k] = 1.0 / ms.scale[k]; }
   if (launch_moments<HYDRO_MOMENTS, unsigned long long>(e, s, K, e->hydro64, pl.path == MomentPath::tiled)) return 1;
   if (read_moments_stats(e)) return 1;                       // (one wait per deterministic call: get_hydro follows)
-  if (e->mom_last[3] > 0) {
+  if (e->mom_stats.last[3] > 0) {
     VH_CHECK(hipMemsetAsync(e->hydro64, 0, sizeof(unsigned long long) * words, e->stream));
     VH_FAIL("accumulate_hydro_p: %lld contributions are out of the fixed-point range of the deterministic sums (a momentum |u| of the order of 2^12 and above); nothing was added",
-            (long long)e->mom_last[3]);
+            (long long)e->mom_stats.last[3]);
   }
   hipLaunchKernelGGL(moments_finalize_kernel<HYDRO_MOMENTS>, dim3((unsigned)((e->gk.nv + 255) / 256)), dim3(256), 0, e->stream,
                      reinterpret_cast<float *>(e->hydro), e->hydro64, e->gk.nv, inv);
@@ -259,10 +253,9 @@ int k_accumulate_hydro_p(Engine *e, Species &s, bool wants_tile) {
 }
 
 int k_accumulate_rho_p(Engine *e, Species &s, bool wants_tile) {
-  if (s.np == 0 || s.chargeless) { book_untiled(e, s); e->mom_last[0] = e->mom_last[2] = 0; return 0; }   // charge-0 copies add nothing
+  if (s.np == 0 || s.chargeless) { book_untiled(e, s); e->mom_stats.last[0] = e->mom_stats.last[2] = 0; return 0; }   // charge-0 copies add nothing
   const MomentPlan pl = plan_for(e, s, wants_tile, e->knobs.rho_per_particle);
   if (!e->det_acc && pl.path != MomentPath::tiled) { book_untiled(e, s); return k_rho_p_untiled(e, s, pl.path == MomentPath::cells); }
-  if (ensure_moments(e)) return 1;
   if (pl.sort_by_tile_first && k_sort_p(e, s, true)) return 1;
   MomK K{};
   K.h.r8V = 0.125 * e->grid.rdx * e->grid.rdy * e->grid.rdz;   // rho_p.c:37

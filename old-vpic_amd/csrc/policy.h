@@ -1,6 +1,7 @@
-// policy.h -- the engine's sort and push decisions (vpic_hip_step, sort_p, advance_p) over plain values: the callers read
-// their HIP events and pinned words once and hand in what they read.  Plain C++17, no HIP: tests/policy_check.cpp builds it
-// with the host compiler alone.
+// policy.h -- the engine's host decisions over plain values: the sort and the push (vpic_hip_step, sort_p, advance_p), whose
+// callers read their HIP events and pinned words once and hand in what they read, the moments, and the launch shapes of the
+// passes over one species (spectrum.hip, distribution.hip).  Plain C++17, no HIP: tests/policy_check.cpp builds it with the
+// host compiler alone.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -279,6 +280,94 @@ inline PushPlan plan_push(Policy &s, const PushInputs &in, int n_seg) {
               : pl.det ? (pl.tiled ? (in.coarse_sorted ? PushInstance::det_tile_only : PushInstance::det_tile) : PushInstance::det_row)
               : !pl.tiled ? (s.wide_window ? PushInstance::row_wide : PushInstance::row_narrow)
               : in.coarse_sorted ? PushInstance::tile_only : pl.fuse ? PushInstance::tile_sort : pl.hist ? PushInstance::tile_hist : PushInstance::tile;
+  return pl;
+}
+
+// ---- the streaming passes over one species (spectrum.hip, distribution.hip): every wavefront takes a contiguous chunk -------
+// chunk of each of `waves` wavefronts that share n particles, a multiple of 64
+inline long long chunk_for(long long n, long long waves) { return ((n + waves - 1) / waves + 63) / 64 * 64; }
+// workgroups of waves_per_group wavefronts for np > 0 particles: 16 passes of 64 per wavefront, 2048 workgroups at the most
+struct Chunks { long long groups = 0, chunk = 0; };
+inline Chunks plan_chunks(long long np, int waves_per_group) {
+  Chunks c;
+  const long long per_group = 64ll * waves_per_group * 16;
+  c.groups = std::min(2048ll, (np + per_group - 1) / per_group);
+  c.chunk = chunk_for(np, c.groups * waves_per_group);
+  return c;
+}
+
+// spectrum.hip: sort keys per window of linear bands (0: no window, every particle adds to global memory)
+constexpr int SPEC_WIN_WORDS = 3072;           // LDS words a wavefront's window of linear bands may take (12 KB)
+constexpr int SPEC_WIN_KEYS = 128;             // ... and the most sort keys it spans
+inline int spectrum_window(int n_lin) {
+  if (n_lin <= 0) return 0;
+  const int win = SPEC_WIN_WORDS / n_lin;
+  return win >= SPEC_WIN_KEYS ? SPEC_WIN_KEYS : win >= 64 ? 64 : 0;   // (a tile's 64 keys at least, or no window)
+}
+
+// distribution.hip: which of the three paths a (checked) descriptor takes, and the window's shape (include/vpic_hip.h states
+// the rule).  n[a], d[a], position[a]: bins, bin width and "is X, Y or Z" of axis a (n[1] = 1 for one axis); lds_bins:
+// VPIC_HIP_DIST_LDS_BINS
+constexpr int DIST_WIN_WORDS = 3072;           // LDS words a wavefront's window may take (12 KB)
+constexpr int DIST_WIN_SPARE_WORDS = 2048;     // ... and up to where it is given DIST_WIN_SPARE bins more than a tile touches
+constexpr int DIST_WIN_SPARE = 3;
+enum { DIST_LDS = 0, DIST_WINDOW = 1, DIST_GLOBAL = 2 };
+struct DistPlan { int path = DIST_LDS, pos_axis = 0, win = 0, n_other = 1; };   // DIST_WINDOW: which axis slides, bins of it per window, bins of the other axis
+inline DistPlan plan_distribution(int n_axes, const int n[2], const double d[2], const bool position[2], int lds_bins) {
+  DistPlan pl;
+  if ((long long)n[0] * n[1] <= lds_bins) return pl;
+  pl.path = DIST_GLOBAL;
+  int pa = -1;
+  for (int a = n_axes - 1; a >= 0; a--) if (position[a]) pa = a;
+  if (pa < 0) return pl;
+  const int n_pos = n[pa], n_other = n[1 - pa];
+  const double tile_bins = ceil((double)TILE_EDGE / d[pa]) + 1.0;             // bins the cells of one tile can touch
+  if (!(tile_bins * n_other <= (double)DIST_WIN_WORDS)) return pl;
+  int win = (int)tile_bins;
+  if ((win + DIST_WIN_SPARE) * n_other <= DIST_WIN_SPARE_WORDS) win += DIST_WIN_SPARE;   // fewer slides along a row of voxels, while it is cheap
+  if (win > n_pos) win = n_pos;
+  pl.path = DIST_WINDOW; pl.pos_axis = pa; pl.win = win; pl.n_other = n_other;
+  return pl;
+}
+
+// DIST_WINDOW on a species in tile order: which particles a wavefront takes.  All tiles with the same tile index along
+// the position axis (a "column") touch the same few bins of it, so a wavefront that takes `group` tiles of ONE column
+// moves its window once and flushes it once for all of them -- a flush adds every non-zero word of the window to global
+// memory, and with one tile per flush (a contiguous chunk of the array) that is one global add for every two
+// particles of the headline case.  Wavefront w < items takes members [(w % groups_per_col) * group, + group) of column
+// w / groups_per_col; what was appended since the sort, [n_sorted, np), is shared out in contiguous chunks of tail_chunk
+// among the wavefronts from item_waves on (a whole number of workgroups: those between items and item_waves take nothing).
+// by_tile false: contiguous chunks (plan_chunks).  fallback_chunk: every wavefront's chunk where tpart[] turns out not to be a
+// partition (k_check_tile_partition).
+constexpr long long DIST_ITEM_PARTICLES = 32768;   // particles a wavefront takes on average, at the most
+struct DistTilePlan {
+  bool by_tile = false;
+  int n_col = 0, members = 0, group = 0, groups_per_col = 0, items = 0, item_waves = 0;   // members: tiles per column
+  long long groups = 0, tail_chunk = 0, fallback_chunk = 0;                             // groups: workgroups of the launch
+};
+// axis: 0 x, 1 y, 2 z; usable: tile_partition_usable (engine.h)
+inline DistTilePlan plan_dist_tiles(int ntx, int nty, int ntz, int axis, bool usable, long long n_sorted, long long np, int waves_per_group) {
+  DistTilePlan pl;
+  if (!usable || n_sorted <= 0) return pl;
+  // tiles per wavefront: 8 (a flush per 8 tiles), more on grids of more than 65 536 tiles, fewer while that leaves
+  // a wavefront more than DIST_ITEM_PARTICLES on average (too few wavefronts for the chip)
+  const int ntiles = ntx * nty * ntz;
+  pl.n_col = axis == 0 ? ntx : axis == 1 ? nty : ntz;
+  pl.members = ntiles / pl.n_col;
+  pl.group = std::min(pl.members, std::max(8, (ntiles + 8191) / 8192));
+  while (pl.group > 1 && (long long)pl.n_col * ((pl.members + pl.group - 1) / pl.group) * DIST_ITEM_PARTICLES < n_sorted)
+    pl.group = (pl.group + 1) / 2;
+  pl.groups_per_col = (pl.members + pl.group - 1) / pl.group;
+  pl.items = pl.n_col * pl.groups_per_col;
+  // still too few wavefronts for the particles (and not a chip's worth of them either): contiguous chunks
+  if (!(pl.items >= 4096 || (long long)pl.items * DIST_ITEM_PARTICLES >= n_sorted)) return pl;
+  pl.by_tile = true;
+  const long long item_groups = (pl.items + waves_per_group - 1) / waves_per_group;
+  pl.item_waves = (int)(item_groups * waves_per_group);
+  const Chunks tail = np > n_sorted ? plan_chunks(np - n_sorted, waves_per_group) : Chunks();
+  pl.tail_chunk = tail.chunk;
+  pl.groups = item_groups + tail.groups;
+  pl.fallback_chunk = chunk_for(np, pl.groups * waves_per_group);
   return pl;
 }
 

@@ -7,6 +7,7 @@
 //   2  select_scan_kernel   one workgroup: the exclusive scan of the chunk counts into 64-bit offsets, and the total
 //   3  select_write_kernel  re-reads the bits (no coordinate), and the kept lanes gather their particle, the fields at
 //                           it and its index to where the scan says
+// The scratch buffers grow with engine.h's grow<T>; the statistics go through its DiagStats like every diagnostic's.
 #include "dist_coords.h"
 #include <algorithm>
 
@@ -168,18 +169,9 @@ void select_write_kernel(ParticlesK p, const int64_t *__restrict__ tag, const in
   }
 }
 
-template <typename T>
-static int grow(T *&buf, size_t &have, size_t want) {
-  if (want <= have) return 0;
-  (void)hipFree(buf); buf = nullptr; have = 0;
-  VH_CHECK(hipMalloc((void **)&buf, want * sizeof(T)));
-  have = want;
-  return 0;
-}
-
 // Launches 1 and 2, and launch 3 when want_p / want_f / want_i ask for an output and a record is to be written: the
 // first min(kept, cap) records are then in Engine::sel_p / sel_f / sel_i (device).  Waits for the stream; fills
-// Engine::sel_last.  count_only: launch 1 stores no masks.  Reads the species and changes nothing about it.
+// Engine::sel_stats.last.  count_only: launch 1 stores no masks.  Reads the species and changes nothing about it.
 int k_species_select(Engine *e, Species &s, const vpic_hip_select_t &d, int64_t cap, bool want_p, bool want_f, bool want_i, bool count_only) {
   SelectK k{};
   k.s = d;
@@ -187,25 +179,22 @@ int k_species_select(Engine *e, Species &s, const vpic_hip_select_t &d, int64_t 
   k.use_tag = (d.flags & (VPIC_HIP_SELECT_TAG_RANGE | VPIC_HIP_SELECT_TAG_EVERY)) != 0;
   const long long np = s.np, n_chunks = (np + SEL_CHUNK - 1) / SEL_CHUNK;
   const int64_t *tag = s.has_tags ? s.tag : nullptr;                         // never allocated: every tag reads 0
-  if (!e->sel_stats) VH_CHECK(hipMalloc((void **)&e->sel_stats, 2 * sizeof(unsigned long long)));
-  if (!e->sel_host) VH_CHECK(hipHostMalloc((void **)&e->sel_host, 2 * sizeof(unsigned long long), hipHostMallocDefault));
   if (grow(e->sel_counts, e->sel_counts_n, (size_t)n_chunks) || grow(e->sel_offsets, e->sel_offsets_n, (size_t)n_chunks)) return 1;
   if (!count_only && grow(e->sel_mask, e->sel_mask_n, (size_t)n_chunks * SEL_GROUPS)) return 1;
-  VH_CHECK(hipMemsetAsync(e->sel_stats, 0, 2 * sizeof(unsigned long long), e->stream));
+  if (e->sel_stats.begin(e->stream)) return 1;
   const unsigned nb = (unsigned)std::min<long long>(n_chunks, SEL_MAX_BLOCKS);
   const TileK tk = make_tile_k(e->gk);
   if (n_chunks > 0) {
     auto mark = count_only ? select_mark_kernel<false> : select_mark_kernel<true>;
     hipLaunchKernelGGL(mark, dim3(nb), dim3(64 * SEL_WAVES), 0, e->stream, s.p, tag, np, n_chunks, k, e->gk, tk,
-                       count_only ? nullptr : e->sel_mask, e->sel_counts, e->sel_stats);
+                       count_only ? nullptr : e->sel_mask, e->sel_counts, e->sel_stats.dev);
     VH_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(256), 0, e->stream, (const unsigned *)e->sel_counts, n_chunks, e->sel_offsets, e->sel_stats);
+    hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(256), 0, e->stream, (const unsigned *)e->sel_counts, n_chunks, e->sel_offsets, e->sel_stats.dev);
     VH_CHECK(hipGetLastError());
   }
-  VH_CHECK(hipMemcpyAsync(e->sel_host, e->sel_stats, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-  VH_CHECK(hipStreamSynchronize(e->stream));
-  const int64_t seen = (int64_t)e->sel_host[0], kept = (int64_t)e->sel_host[1];
-  const int64_t n_out = std::min(kept, cap);
+  if (e->sel_stats.read(e->stream)) return 1;              // {seen, kept}; [2] and [3] are filled in below
+  int64_t *last = e->sel_stats.last;
+  const int64_t n_out = std::min(last[1], cap);
   int64_t written = 0;
   if (!count_only && n_out > 0 && (want_p || want_f || want_i)) {
     if (want_p && grow(e->sel_p, e->sel_p_n, (size_t)n_out)) return 1;
@@ -218,7 +207,7 @@ int k_species_select(Engine *e, Species &s, const vpic_hip_select_t &d, int64_t 
     VH_CHECK(hipGetLastError());
     written = n_out;
   }
-  e->sel_last[0] = seen; e->sel_last[1] = kept; e->sel_last[2] = written; e->sel_last[3] = n_chunks;
+  last[2] = written; last[3] = n_chunks;
   return 0;
 }
 

@@ -2,18 +2,17 @@
 // vpic_hip_energy_bands; include/vpic_hip.h).  What the production deck's diagnostic computes on the host
 // (decks/trecon-part/energy.cxx:96-108 the counting, :116-162 the normalisation and the ghost fill), as one
 // streaming pass over i, ux, uy, uz (16 B per particle).  Every counter is an integer: the result does not depend
-// on the order of the array nor on which kernel instance pushed it.
+// on the order of the array nor on which kernel instance pushed it.  The window's size and the launch shape are host
+// decisions in policy.h (spectrum_window, plan_chunks); the window protocol, add_together and the statistics block are
+// the ones every pass over a species uses (engine.h).
 #include "engine.h"
 
 namespace vpichip {
 
 constexpr int SPEC_WAVES = 4;                  // wavefronts per workgroup
-constexpr int SPEC_WIN_WORDS = 3072;           // LDS words a wavefront's window of linear bands may take (12 KB)
-constexpr int SPEC_WIN_KEYS = 128;             // ... and the most sort keys it spans
-constexpr int SPEC_BACKOFF = 16;               // passes a wavefront leaves its window where it is after a slide did not help
 
 struct SpectrumK {
-  int n_lin, n_log, win;                       // win: sort keys per window (0: no window, every particle adds to global memory)
+  int n_lin, n_log, win;                       // win: sort keys per window (policy.h, spectrum_window; 0: no window, every particle adds to global memory)
   double d_lin, log_lo, d_log;
 };
 
@@ -56,9 +55,7 @@ __device__ __forceinline__ void flush_window(unsigned *win, int base, const Spec
 // the window add there; if some are not, the window is flushed and moved to the key of the first of them (in an
 // ordered array the smallest), and they try again, twice at the most (two slides: 64 particles that straddle a
 // boundary between tiles, or the ghost voxels between two rows or planes, still all hit); what does not fit then adds
-// to global memory and is counted as a miss.  When more than half the wavefront still misses after that, the
-// window stays where it is for the next SPEC_BACKOFF passes (an array in no order: the window cannot help, and
-// flushing it every pass would only cost).
+// to global memory and is counted as a miss (the protocol: engine.h, window_add).
 // stats[0]: live particles seen, stats[1]: misses.
 template <bool TILE>
 __global__ __launch_bounds__(64 * SPEC_WAVES)
@@ -75,8 +72,7 @@ void energy_spectrum_kernel(const int *__restrict__ pi, const float *__restrict_
 
   const long long w = (long long)blockIdx.x * SPEC_WAVES + wave;
   const long long begin = w * chunk, end = begin + chunk < np ? begin + chunk : np;
-  int base = 0, backoff = 0;
-  bool placed = false;                                                       // the window has been given a place
+  SlideWindow w_state;
   unsigned long long n_seen = 0, n_miss = 0;
   for (long long at = begin; at < end; at += 64) {
     const long long idx = at + lane;
@@ -108,39 +104,24 @@ void energy_spectrum_kernel(const int *__restrict__ pi, const float *__restrict_
         if (TILE) {
           // sort_key files a voxel of a ghost layer under the nearest interior cell: such a particle is counted in
           // its own voxel, through global memory
-          const int cz = (int)(__umulhi((unsigned)voxel, t.mul_sz) >> t.sh_sz), rem = voxel - cz * t.sz;
-          const int cy = (int)(__umulhi((unsigned)rem, t.mul_sy) >> t.sh_sy), cx = rem - cy * t.sy;
+          int cx, cy, cz;
+          voxel_cell(voxel, t, cx, cy, cz);
           if (cx < 1 || cx > g.nx || cy < 1 || cy > g.ny || cz < 1 || cz > g.nz) key = -1;
         }
       }
-      for (int round = 0; round < 3 && k.win > 0; round++) {
-        if (round > 0) {
-          const unsigned long long left = __ballot(pending && key >= 0);
-          if (!left) break;
-          if (backoff > 0) { backoff--; break; }
-          if (placed) flush_window<TILE>(win, base, k, g, t, lin, lane);
-          const int first = __builtin_amdgcn_readlane(key, __ffsll((long long)left) - 1);
-          base = TILE ? first & ~63 : first;                                 // a tile's cells come in any order when it is sorted by tile only
-          placed = true;
-        }
-        const bool hit = placed && pending && key >= base && key < base + k.win;
-        if (hit) {
-          // most of a wavefront is in one voxel and one band: the lanes that share the first hit's word add once, together
-          // (more rounds of this, word by word, measured slower than letting the others add for themselves)
-          const int a = (key - base) * k.n_lin + band;
-          const int lead = __ffsll((long long)__ballot(hit)) - 1, a0 = __shfl(a, lead);
-          const unsigned long long same = __ballot(a == a0);
-          if (a != a0) atomicAdd(win + a, 1u);
-          else if (lane == lead) atomicAdd(win + a, (unsigned)__popcll(same));
-          pending = false;
-        }
-        if (round == 2 && __popcll(__ballot(pending)) > 32) backoff = SPEC_BACKOFF;
-      }
+      // the window goes to the key of the first lane still waiting (in an ordered array the smallest); key < 0 never slides it
+      if (k.win > 0)
+        pending = window_add(w_state, win, k.win, k.n_lin, key, band, pending, lane,
+          [&](unsigned long long left) {
+            const int first = __builtin_amdgcn_readlane(key, __ffsll((long long)left) - 1);
+            return TILE ? first & ~63 : first;                               // a tile's cells come in any order when it is sorted by tile only
+          },
+          [&](int base) { flush_window<TILE>(win, base, k, g, t, lin, lane); });
       if (pending) atomicAdd(lin + (size_t)band * g.nv + voxel, 1u);
       n_miss += __popcll(__ballot(pending));
     }
   }
-  if (k.n_lin > 0 && k.win > 0 && placed) flush_window<TILE>(win, base, k, g, t, lin, lane);
+  if (k.n_lin > 0 && k.win > 0 && w_state.placed) flush_window<TILE>(win, w_state.base, k, g, t, lin, lane);
   if (lane == 0 && n_seen) { atomicAdd(&stats[0], n_seen); if (n_miss) atomicAdd(&stats[1], n_miss); }
   __syncthreads();
   for (int j = threadIdx.x; j < k.n_log; j += 64 * SPEC_WAVES)
@@ -162,55 +143,31 @@ void energy_bands_kernel(const unsigned *__restrict__ lin, float *__restrict__ b
     bands[(size_t)b * g.nv + v] = n ? (float)((double)lin[(size_t)b * g.nv + src] / (double)n) : 0.f;
 }
 
-static int ensure_spectrum(Engine *e, size_t lin_words, size_t log_words) {
-  if (!e->spec_stats) {
-    VH_CHECK(hipMalloc((void **)&e->spec_stats, 2 * sizeof(unsigned long long)));
-    VH_CHECK(hipHostMalloc((void **)&e->spec_host, (2 + VPIC_HIP_SPECTRUM_MAX_LOG) * sizeof(unsigned long long), hipHostMallocDefault));
-    VH_CHECK(hipMalloc((void **)&e->spec_log, VPIC_HIP_SPECTRUM_MAX_LOG * sizeof(unsigned long long)));
-  }
-  (void)log_words;
-  if (lin_words > e->spec_lin_words) {
-    (void)hipFree(e->spec_lin); (void)hipFree(e->spec_bands);
-    e->spec_lin = nullptr; e->spec_bands = nullptr; e->spec_lin_words = 0;
-    VH_CHECK(hipMalloc((void **)&e->spec_lin, lin_words * sizeof(unsigned)));
-    VH_CHECK(hipMalloc((void **)&e->spec_bands, lin_words * sizeof(float)));
-    e->spec_lin_words = lin_words;
-  }
-  return 0;
-}
-
-// counts of species s into Engine::spec_lin / spec_log (device); the statistics land in spec_host[0..1], the log
-// counts in spec_host[2..] (pinned), after the stream has been waited for
+// counts of species s into Engine::spec_lin / spec_log (device); the log counts land in spec_log_host (pinned), after the
+// stream has been waited for
 int k_energy_spectrum(Engine *e, Species &s, const vpic_hip_spectrum_t &sp) {
   const size_t lin_words = (size_t)sp.n_lin * (size_t)e->gk.nv;
-  if (ensure_spectrum(e, lin_words, (size_t)sp.n_log)) return 1;
+  if (!e->spec_log) VH_CHECK(hipMalloc((void **)&e->spec_log, VPIC_HIP_SPECTRUM_MAX_LOG * sizeof(unsigned long long)));
+  if (!e->spec_log_host) VH_CHECK(hipHostMalloc((void **)&e->spec_log_host, VPIC_HIP_SPECTRUM_MAX_LOG * sizeof(unsigned long long), hipHostMallocDefault));
+  size_t bands_words = e->spec_lin_words;                                     // (the two grow together: one size for both)
+  if (grow(e->spec_lin, e->spec_lin_words, lin_words) || grow(e->spec_bands, bands_words, lin_words)) { e->spec_lin_words = 0; return 1; }
+  if (e->spec_stats.begin(e->stream)) return 1;
   SpectrumK k{};
   k.n_lin = sp.n_lin; k.n_log = sp.n_log; k.d_lin = sp.d_lin; k.log_lo = sp.log_lo; k.d_log = sp.d_log;
-  if (sp.n_lin > 0) {
-    k.win = SPEC_WIN_WORDS / sp.n_lin;
-    k.win = k.win >= SPEC_WIN_KEYS ? SPEC_WIN_KEYS : k.win >= 64 ? 64 : 0;   // (a tile's 64 keys at least, or no window)
-  }
-  VH_CHECK(hipMemsetAsync(e->spec_stats, 0, 2 * sizeof(unsigned long long), e->stream));
+  k.win = spectrum_window(sp.n_lin);
   if (lin_words) VH_CHECK(hipMemsetAsync(e->spec_lin, 0, lin_words * sizeof(unsigned), e->stream));
   if (sp.n_log) VH_CHECK(hipMemsetAsync(e->spec_log, 0, (size_t)sp.n_log * sizeof(unsigned long long), e->stream));
   if (s.np > 0) {
-    const long long per_group = 64ll * SPEC_WAVES * 16;
-    long long nb = (s.np + per_group - 1) / per_group;
-    if (nb > 2048) nb = 2048;
-    const long long waves = nb * SPEC_WAVES;
-    const long long chunk = ((s.np + waves - 1) / waves + 63) / 64 * 64;
+    const Chunks ch = plan_chunks(s.np, SPEC_WAVES);
     const size_t lds = sizeof(unsigned) * ((size_t)sp.n_log + (size_t)SPEC_WAVES * k.win * sp.n_lin);
     const TileK tk = make_tile_k(e->gk);
     auto kernel = s.tile_valid ? energy_spectrum_kernel<true> : energy_spectrum_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(64 * SPEC_WAVES), lds, e->stream, s.p.i, s.p.ux, s.p.uy, s.p.uz,
-                       (long long)s.np, chunk, k, e->gk, tk, e->spec_lin, e->spec_log, e->spec_stats);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)ch.groups), dim3(64 * SPEC_WAVES), lds, e->stream, s.p.i, s.p.ux, s.p.uy, s.p.uz,
+                       (long long)s.np, ch.chunk, k, e->gk, tk, e->spec_lin, e->spec_log, e->spec_stats.dev);
     VH_CHECK(hipGetLastError());
   }
-  VH_CHECK(hipMemcpyAsync(e->spec_host, e->spec_stats, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-  if (sp.n_log) VH_CHECK(hipMemcpyAsync(e->spec_host + 2, e->spec_log, (size_t)sp.n_log * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-  VH_CHECK(hipStreamSynchronize(e->stream));
-  e->spec_last[0] = (int64_t)e->spec_host[0]; e->spec_last[1] = (int64_t)e->spec_host[1];
-  return 0;
+  if (sp.n_log) VH_CHECK(hipMemcpyAsync(e->spec_log_host, e->spec_log, (size_t)sp.n_log * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+  return e->spec_stats.read(e->stream);
 }
 
 int k_energy_bands(Engine *e, int n_lin) {

@@ -1,4 +1,5 @@
-// The engine's sort and push decisions (old-vpic_amd/csrc/policy.h) on the host: one case per rule the code states.
+// The engine's host decisions (old-vpic_amd/csrc/policy.h) -- sort, push, and the launch shapes of the passes over one
+// species -- on the host: one case per rule the code states.
 // usage: policy_check [case ...] (no case: all of them; --list: their names).  Prints "ok <case>" or "FAIL <case>: ..." lines.
 #include <cstdio>
 #include <cstring>
@@ -274,11 +275,129 @@ static void early() {
   CHECK(p.early_sorts == 1);
 }
 
+// ---- the passes over one species (spectrum.hip, distribution.hip) ----
+static void chunks() {
+  const int W = 4;
+  const long long G = 64ll * W * 16;
+  for (long long np : {1ll, 63ll, 64ll, G, G + 1, 2048 * G, 2048 * G + 1, (1ll << 31) - 8192}) {
+    const Chunks c = plan_chunks(np, W);
+    // what k_energy_spectrum and k_species_distribution each wrote out before they shared this
+    long long nb = (np + G - 1) / G;
+    if (nb > 2048) nb = 2048;
+    const long long waves = nb * W, chunk = ((np + waves - 1) / waves + 63) / 64 * 64;
+    CHECK(c.groups == nb && c.chunk == chunk);
+    CHECK(c.groups >= 1 && c.groups <= 2048 && c.chunk % 64 == 0 && c.groups * W * c.chunk >= np);
+  }
+  CHECK(plan_chunks(G, W).groups == 1 && plan_chunks(G + 1, W).groups == 2 && plan_chunks(2048 * G + 1, W).groups == 2048);
+}
+
+static void spectrum_window_rule() {
+  // 3072 / n_lin keys: 128 of them while there are that many, 64 while there are that many, else no window
+  CHECK(spectrum_window(1) == 128 && spectrum_window(24) == 128);     // 3072 / 24 = 128
+  CHECK(spectrum_window(25) == 64 && spectrum_window(48) == 64);      // 122, 64
+  CHECK(spectrum_window(49) == 0 && spectrum_window(3073) == 0);      // 62, 0
+  CHECK(spectrum_window(0) == 0);                                     // no linear bands
+}
+
+static DistPlan dist_plan(int n0, double d0, bool pos0, int n1 = 1, double d1 = 1, bool pos1 = false, int lds_bins = 8192) {   // 8192: VPIC_HIP_DIST_LDS_BINS
+  const int n[2] = {n0, n1}; const double d[2] = {d0, d1}; const bool pos[2] = {pos0, pos1};
+  return plan_distribution(n1 > 1 || pos1 ? 2 : 1, n, d, pos, lds_bins);
+}
+static void distribution_path() {
+  // the whole histogram in LDS up to VPIC_HIP_DIST_LDS_BINS bins, whatever the axes
+  CHECK(dist_plan(8192, 1, true).path == DIST_LDS && dist_plan(128, 1, true, 64, 1, false).path == DIST_LDS);
+  CHECK(dist_plan(8193, 1, false).path == DIST_GLOBAL && dist_plan(128, 1, false, 65, 1, false).path == DIST_GLOBAL);   // no position axis
+  // a position axis first: half a cell per bin, ceil(4 / 0.5) + 1 = 9 bins x 256 = 2304 words; no room for the spare three
+  DistPlan pl = dist_plan(256, 0.5, true, 256, 0.01, false);
+  CHECK(pl.path == DIST_WINDOW && pl.pos_axis == 0 && pl.win == 9 && pl.n_other == 256);
+  // ... second: ceil(4 / 0.75) + 1 = 7 bins x 100, and the spare three
+  pl = dist_plan(100, 0.01, false, 126, 0.75, true);
+  CHECK(pl.path == DIST_WINDOW && pl.pos_axis == 1 && pl.win == 10 && pl.n_other == 100);
+  // both: the first one slides
+  pl = dist_plan(128, 1, true, 128, 1, true);
+  CHECK(pl.path == DIST_WINDOW && pl.pos_axis == 0 && pl.win == 8 && pl.n_other == 128);
+  // a tile's bins x the other axis: at 3072 words the window, above global adds (0.9 cells: 6 bins; 2 cells: 3 bins)
+  CHECK(dist_plan(64, 0.9, true, 512, 1, false).path == DIST_WINDOW && dist_plan(64, 0.9, true, 512, 1, false).win == 6);
+  CHECK(dist_plan(64, 0.9, true, 513, 1, false).path == DIST_GLOBAL);
+  CHECK(dist_plan(1024, 1, false, 64, 2.0, true).path == DIST_WINDOW && dist_plan(1025, 1, false, 64, 2.0, true).path == DIST_GLOBAL);
+  // the three spare bins: granted while (5 + 3) x the other axis stays within 2048 words
+  CHECK(dist_plan(64, 1, true, 256, 1, false).win == 8 && dist_plan(64, 1, true, 257, 1, false).win == 5);
+  CHECK(dist_plan(64, 1, true, 257, 1, false).path == DIST_WINDOW);
+  // win never exceeds the axis (with VPIC_HIP_DIST_LDS_BINS as it is such a histogram is held in LDS: a lower bound shows it)
+  pl = dist_plan(4, 1, true, 8, 1, false, 16);
+  CHECK(pl.path == DIST_WINDOW && pl.win == 4 && pl.n_other == 8);
+  CHECK(dist_plan(8, 1, true, 8, 1, false, 16).win == 8 && dist_plan(9, 1, true, 8, 1, false, 16).win == 8);
+}
+
+// every wavefront of the launch as species_distribution_kernel<DIST_WINDOW> deals them (distribution.hip: "what this wavefront takes")
+static void walk_dist_tiles(int ntx, int nty, int ntz, int axis, long long n_sorted, long long np, bool expect_by_tile) {
+  const int W = 4, ntiles = ntx * nty * ntz;
+  const DistTilePlan pl = plan_dist_tiles(ntx, nty, ntz, axis, true, n_sorted, np, W);
+  CHECK(pl.by_tile == expect_by_tile);
+  if (!pl.by_tile) return;
+  CHECK(pl.item_waves % W == 0 && pl.item_waves >= pl.items && pl.item_waves < pl.items + W);
+  CHECK(pl.n_col * pl.members == ntiles && pl.groups_per_col * pl.n_col == pl.items);
+  std::vector<int> taken(ntiles, 0);
+  long long tail_to = n_sorted, fallback_to = 0;
+  const long long waves = pl.groups * W;
+  for (long long w = 0; w < waves; w++) {
+    CHECK(w * pl.fallback_chunk == fallback_to || w * pl.fallback_chunk >= np);   // the fallback chunks follow one another from 0 on
+    fallback_to = std::max(fallback_to, std::min(w * pl.fallback_chunk + pl.fallback_chunk, np));
+    if (w < pl.items) {
+      const int col = (int)w / pl.groups_per_col, first_member = ((int)w - col * pl.groups_per_col) * pl.group;
+      const int n_seg = std::min(pl.group, pl.members - first_member);
+      CHECK(n_seg >= 1);                                   // no item is empty
+      for (int seg = 0; seg < n_seg; seg++) {
+        const int m = first_member + seg;
+        int tx, ty, tz;
+        if (axis == 0) { tx = col; ty = m % nty; tz = m / nty; }
+        else if (axis == 1) { ty = col; tx = m % ntx; tz = m / ntx; }
+        else { tz = col; tx = m % ntx; ty = m / ntx; }
+        CHECK(tx >= 0 && tx < ntx && ty >= 0 && ty < nty && tz >= 0 && tz < ntz);
+        const int tile = (tz * nty + ty) * ntx + tx;
+        if (tile >= 0 && tile < ntiles) taken[tile]++;
+      }
+    } else if (w >= pl.item_waves) {
+      const long long begin = n_sorted + (w - pl.item_waves) * pl.tail_chunk;
+      CHECK(begin == tail_to || begin >= np);              // the chunks follow one another from n_sorted on
+      tail_to = std::max(tail_to, std::min(begin + pl.tail_chunk, np));
+    }
+  }
+  for (int c : taken) CHECK(c == 1);                       // every tile exactly once
+  CHECK(tail_to == np && fallback_to == np);               // [n_sorted, np) and, where tpart[] is no partition, [0, np)
+  CHECK(pl.fallback_chunk % 64 == 0 && pl.tail_chunk % 64 == 0 && (pl.tail_chunk > 0) == (np > n_sorted));
+  CHECK(pl.groups == pl.item_waves / W + (np > n_sorted ? plan_chunks(np - n_sorted, W).groups : 0));
+}
+static void distribution_tiles() {
+  const int grids[3][3] = {{1, 1, 1}, {3, 2, 1}, {24, 2, 2}};
+  for (auto &g : grids)
+    for (int axis = 0; axis < 3; axis++) {
+      const long long items_most = (long long)g[0] * g[1] * g[2];              // with one tile per wavefront
+      walk_dist_tiles(g[0], g[1], g[2], axis, 1000, 1000, true);               // a few particles, nothing appended
+      walk_dist_tiles(g[0], g[1], g[2], axis, 1000, 1000 + 64 * 4 * 16 * 3 + 1, true);   // ... four workgroups' worth appended
+      walk_dist_tiles(g[0], g[1], g[2], axis, items_most * DIST_ITEM_PARTICLES, items_most * DIST_ITEM_PARTICLES + 5, true);   // group halved down to 1
+      // fallback (i): more than DIST_ITEM_PARTICLES per wavefront even with one tile each, and fewer than 4096 wavefronts
+      walk_dist_tiles(g[0], g[1], g[2], axis, items_most * DIST_ITEM_PARTICLES + 1, items_most * DIST_ITEM_PARTICLES + 1, false);
+    }
+  // the group is halved only as far as needed: 24 columns of 4 tiles, 10^6 particles -> two tiles per wavefront
+  DistTilePlan pl = plan_dist_tiles(24, 2, 2, 0, true, 1000000, 1000000, 4);
+  CHECK(pl.by_tile && pl.group == 2 && pl.groups_per_col == 2 && pl.items == 48 && pl.item_waves == 48 && pl.tail_chunk == 0);
+  pl = plan_dist_tiles(24, 2, 2, 0, true, 1000, 1000, 4);
+  CHECK(pl.group == 4 && pl.items == 24);
+  // 4096 wavefronts fill the chip whatever they hold: by tile
+  walk_dist_tiles(64, 64, 1, 0, 200000000, 200000000, true);
+  CHECK(plan_dist_tiles(64, 64, 1, 0, true, 200000000, 200000000, 4).items == 4096);
+  // fallback (ii): tpart[] is not usable, or nothing is sorted
+  CHECK(!plan_dist_tiles(3, 2, 1, 0, false, 1000, 1000, 4).by_tile && plan_dist_tiles(3, 2, 1, 0, false, 1000, 1000, 4).items == 0);
+  CHECK(!plan_dist_tiles(3, 2, 1, 0, true, 0, 1000, 4).by_tile);
+}
+
 static const std::vector<std::pair<const char *, std::function<void()>>> cases = {
   {"row_window", row_window}, {"passes_per_wavefront", passes_per_wavefront}, {"tile_imbalance", tile_imbalance},
   {"stage", stage}, {"histogram", histogram}, {"sort_inside_fallback", sort_inside_fallback}, {"tail_regrouping", tail_regrouping},
   {"instance", instance}, {"tile_order", tile_order}, {"flavour", flavour}, {"sort_plan", sort_plan},
   {"sort_inside_or_before", sort_inside_or_before}, {"sort_due_rule", sort_due_rule}, {"early_sort", early},
+  {"chunks", chunks}, {"spectrum_window", spectrum_window_rule}, {"distribution_path", distribution_path}, {"distribution_tiles", distribution_tiles},
 };
 
 int main(int argc, char **argv) {

@@ -22,7 +22,6 @@ import ctypes as C
 import functools
 import importlib
 import os
-import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
@@ -35,19 +34,13 @@ for _p in (ROOT, HERE):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import species_states  # noqa: E402
+from species_states import N_TAIL, STATES, package  # noqa: E402
 from test_distribution_ref import GRID, N, SEED, VTH, descriptors, dist_inputs, distribution_ref, log_margin  # noqa: E402
 from test_spectrum_ref import voxel  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-N_TAIL, N_DOOMED = 5000, 300
-STATES = ["unsorted", "voxel", "tile", "tile_only", "tile_tail_holes"]
 IN_LDS, WINDOW, GLOBAL = "acdg", "bf", "e"
-
-
-def package():
-    v = importlib.import_module("old-vpic_amd")
-    assert v.lib().vpic_hip_device_count() > 0, "no HIP device"
-    return v
 
 
 @functools.lru_cache(maxsize=None)
@@ -58,46 +51,16 @@ def reference_of_the_inputs():
 
 
 def build_state(V, L, state):
-    """(engine, species) with the test's particles in the array state asked for"""
-    nx, ny, nz = GRID
+    """(engine, species) with the test's particles in the array state asked for (species_states.build_state)"""
     holes = state == "tile_tail_holes"
-    kw = dict(pbc=[L.ABSORB_PARTICLES, 0, 0, L.ABSORB_PARTICLES, 0, 0]) if holes else {}
-    e = V.Engine(V.make_grid(nx, ny, nz, float(nx), float(ny), float(nz), np.float32(0.02 if holes else 0.4), **kw))
-    e.set_vacuum()
-    e.load_interpolator()                                   # zero fields: the push leaves the momenta alone
-    sp = e.new_species(-1.0, N + N_TAIL + N_DOOMED + 4096, 8192)
     p = dist_inputs(SEED, N, VTH, GRID, spread=0.95 if holes else 1.0)
     p["tag"] = np.arange(N) + 1
+    tail = None
     if holes:
-        # 300 more, on their way through the absorbing +x wall (0.99 + 2 * 0.95 * 0.02 > 1)
-        rng = np.random.default_rng(5)
-        d = np.zeros(N_DOOMED, L.particle_t)
-        d["i"] = voxel(nx, rng.integers(1, ny + 1, N_DOOMED), rng.integers(1, nz + 1, N_DOOMED), GRID)
-        d["dx"], d["ux"], d["q"] = 0.99, 3.0, -0.01
-        d["tag"] = np.arange(N_DOOMED) + 10 ** 7
-        p = np.concatenate([p, d])
-    e.set_particles(sp, p)
-    if state == "voxel":
-        e.sort_p(sp)
-        assert e.species_order(sp) == "voxel"
-    if state in ("tile", "tile_only", "tile_tail_holes"):
-        e.set_sort_order("engine")
-        e.sort_p(sp)
-        assert e.species_order(sp) == "tile"
-        assert e.species_stats(sp)["by_tile_only"] == (1 if state == "tile_only" else 0)
-    if holes:
-        t = dist_inputs(SEED + 1, N_TAIL, VTH, GRID, spread=0.95)
-        t["tag"] = np.arange(N_TAIL) + 2 * 10 ** 7
-        e.append_particles(sp, t)
-        e.clear_accumulators()
-        e.exchange_begin()
-        e.advance_p_async(sp)
-        e.exchange_pack([0] * 6, [0] * 6, 8192)
-        e.exchange_finish([])
-        assert e.exchange_flags == 0
-        assert e.species_stats(sp)["dead_slots"] == N_DOOMED
-        assert e.np(sp) == N + N_TAIL
-    return e, sp
+        tail = dist_inputs(SEED + 1, N_TAIL, VTH, GRID, spread=0.95)
+        tail["tag"] = np.arange(N_TAIL) + 2 * 10 ** 7
+    # the doomed 300: 0.99 + 2 * 0.95 * 0.02 > 1, through the wall
+    return species_states.build_state(V, state, p, GRID, tail, dt=0.02 if holes else 0.4, doomed_dx=0.99)
 
 
 def check_state(state):
@@ -142,14 +105,7 @@ def check_state(state):
 
 
 def run_child(args, timeout):
-    env = dict(os.environ)
-    if args[0] == "tile_only":
-        env["VPIC_HIP_TILE_COARSE"] = "1"
-    r = subprocess.run([sys.executable, os.path.abspath(__file__)] + [str(a) for a in args], env=env, capture_output=True,
-                       text=True, timeout=timeout)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
-    assert "child OK" in r.stdout
+    species_states.run_child(__file__, args, timeout)
 
 
 @pytest.mark.parametrize("state", STATES)

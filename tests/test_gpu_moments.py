@@ -31,6 +31,8 @@ for _p in (ROOT, HERE):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+from species_states import package  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 ACC_TOL = 2e-6
 GRID = (10, 7, 3)
@@ -40,12 +42,6 @@ N_TAIL, N_DOOMED = 600, 60
 SEED = 20261017
 STATES = ["unsorted", "voxel", "unsorted_wants_tile", "tile", "tile_only", "tile_tail_holes"]
 IN_TILE_ORDER = ("unsorted_wants_tile", "tile", "tile_only", "tile_tail_holes")
-
-
-def package():
-    v = importlib.import_module("old-vpic_amd")
-    assert v.lib().vpic_hip_device_count() > 0, "no HIP device"
-    return v
 
 
 def oracle():

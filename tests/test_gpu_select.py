@@ -16,7 +16,6 @@ import ctypes as C
 import functools
 import importlib
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -28,8 +27,10 @@ for _p in (ROOT, HERE):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import species_states  # noqa: E402
+from species_states import N_DOOMED, N_TAIL, STATES, package  # noqa: E402
 from test_distribution_ref import GRID, N, SEED, VTH, coordinate, dist_inputs  # noqa: E402
-from test_gpu_distribution import N_DOOMED, N_TAIL, STATES, build_state, package  # noqa: E402
+from test_gpu_distribution import build_state  # noqa: E402
 from test_select_ref import INF, fields_ref, keep_mask, random_interpolator, select_ref, selections  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -88,14 +89,7 @@ def check_state(state):
 
 
 def run_child(args, timeout):
-    env = dict(os.environ)
-    if args[0] == "tile_only":
-        env["VPIC_HIP_TILE_COARSE"] = "1"
-    r = subprocess.run([sys.executable, os.path.abspath(__file__)] + [str(a) for a in args], env=env, capture_output=True,
-                       text=True, timeout=timeout)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
-    assert "child OK" in r.stdout
+    species_states.run_child(__file__, args, timeout)
 
 
 @pytest.mark.parametrize("state", STATES)

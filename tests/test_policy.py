@@ -1,4 +1,4 @@
-"""The engine's sort and push decisions (old-vpic_amd/csrc/policy.h) without a GPU: tests/policy_check.cpp, built with the
+"""The engine's host decisions (old-vpic_amd/csrc/policy.h: sort, push, the launch shapes of the species diagnostics) without a GPU: tests/policy_check.cpp, built with the
 host compiler, drives one named case per rule."""
 import os
 import subprocess
@@ -8,7 +8,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = ["row_window", "passes_per_wavefront", "tile_imbalance", "stage", "histogram", "sort_inside_fallback",
          "tail_regrouping", "instance", "tile_order", "flavour", "sort_plan", "sort_inside_or_before", "sort_due_rule",
-         "early_sort"]
+         "early_sort", "chunks", "spectrum_window", "distribution_path", "distribution_tiles"]
 
 
 @pytest.fixture(scope="module")

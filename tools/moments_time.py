@@ -8,57 +8,35 @@ atomic per node and particle; there was no deterministic hydro), "tiled" without
   (d) deterministic accumulate_rho_p per particle / by tile        (e) float accumulate_rho_p before (+ the tile sort) / by tile
 The calls alternate; each is timed with events on the engine's stream, medians over the repeats after a warm-up.
     python tools/moments_time.py [--out profiles/moments_time.txt] [--reps 10]        (GPU box)"""
-import argparse
-import importlib
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import diag_timing as T
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--cells", type=int, default=128)
-    ap.add_argument("--ppc", type=int, default=32)
+    ap = T.parser(reps=10)
     ap.add_argument("--steps", type=int, default=3)
     args = ap.parse_args()
-    import torch
-    V = importlib.import_module("old-vpic_amd")
     n, ppc = args.cells, args.ppc
     np_ = n ** 3 * ppc
 
     def engine(tiled):
         if not tiled:
             os.environ["VPIC_HIP_MOMENTS_TILED"] = "0"        # (read when the engine is created)
-        e = V.Engine(V.make_grid(n, n, n, float(n), float(n), float(n), np.float32(0.95 / np.sqrt(3.0))))
+        _, e, sp, _, stream = T.species(args)
         os.environ.pop("VPIC_HIP_MOMENTS_TILED", None)
-        e.set_vacuum()
-        e.set_sort_order("engine")
-        sp = e.new_species(-1.0, np_ + 4096, np_ // 8)
-        e.load_maxwellian(sp, ppc, 1, -1.0 / ppc, (0.2, 0.0, 0.0), 0.02)
-        e.load_interpolator()
-        e.sort_p(sp)
         e.clear_accumulators()
         for _ in range(args.steps):
             e.advance_p(sp)
         assert e.species_order(sp) == "tile" and e.nm(sp) == 0
-        return e, sp, torch.cuda.ExternalStream(e.stream(), device=torch.device("cuda", 0))
+        return e, sp, stream
 
     before, tiled = engine(False), engine(True)
 
     def timed(side, fn):
-        stream = side[2]
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        fn(side[0], side[1])
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b)
+        return T.timed(side[2], lambda: fn(side[0], side[1]))[0]
 
     def resort(e, sp):
         e.sort_p(sp)
@@ -99,10 +77,9 @@ def main():
     for e, _, _ in (before, tiled):
         e.close()
 
-    lines = [f"hydro moments and rho of one species: {n}^3 cells x {ppc} per cell = {np_} particles, tile order, {args.steps} pushes since the sort, {args.reps} alternating repeats",
-             f"device: {torch.cuda.get_device_name(0)}",
-             "milliseconds: median [min .. max] between events on the engine's stream around the call; '+ sort': the sort by tile that puts",
-             "  the species back into the order the push needs, timed the same way right after the call; statistics: live, through LDS, through global memory, out of range"]
+    lines = T.header("hydro moments and rho", args, f"{args.steps} pushes since the sort, ")
+    lines += ["milliseconds: median [min .. max] between events on the engine's stream around the call; '+ sort': the sort by tile that puts",
+              "  the species back into the order the push needs, timed the same way right after the call; statistics: live, through LDS, through global memory, out of range"]
     med = {}
     for k, v in ms.items():
         t, t2 = np.array([x[0] for x in v]), np.array([x[1] for x in v])
@@ -118,11 +95,7 @@ def main():
     lines.append(f"rho: deterministic by tile / per particle = {d1 / d0:.2f} ({d1 * 26e6 / np_:.2f} ms per 26 M particles; hoped for: well under the 9.6 ms of"
                  f" profiles/r04_production_deck_slab_kernel_stats.csv)   float by tile / before = {e1 / e0:.2f}")
     lines.append(f"decision (float mode keeps the path there was before where the tile path is not faster): hydro {'by tile' if b < a else 'AS BEFORE'}, rho {'by tile' if e1 < e0 else 'AS BEFORE'}")
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    T.finish(lines, args.out)
 
 
 if __name__ == "__main__":

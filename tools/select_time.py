@@ -16,46 +16,26 @@ selection that still holds the copy of its records to the host, so the kernels b
 Expectation to report against: launch 1 reads what (d) reads and writes 1 bit per particle; launch 3 reads np / 8 bytes
 and 48 B per kept particle; so the kernels of (a) together should cost little more than the kernel of (d).
     python tools/select_time.py [--out profiles/select_time.txt] [--reps 20]        (GPU box)"""
-import argparse
-import importlib
-import os
-import sys
-import time
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import diag_timing as T
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--cells", type=int, default=128)
-    ap.add_argument("--ppc", type=int, default=32)
+    ap = T.parser(reps=20)
     ap.add_argument("--no-route-e", action="store_true", help="leave (e) out (runs under a profiler)")
     ap.add_argument("--only", default=None, help="selections to run beside (a), (a0) and (d), e.g. 'b' or 'c,cf' or '' (so that a kernel trace's "
                                                  "per-kernel averages are those of one selection)")
     args = ap.parse_args()
-    import torch
-    V = importlib.import_module("old-vpic_amd")
-    n, ppc, vth = args.cells, args.ppc, 0.02
-    e = V.Engine(V.make_grid(n, n, n, float(n), float(n), float(n), np.float32(0.95 / np.sqrt(3.0))))
-    e.set_vacuum()
-    e.set_sort_order("engine")
+    n, ppc = args.cells, args.ppc
     np_ = n ** 3 * ppc
-    sp = e.new_species(-1.0, np_ + 4096, np_ // 8)
-    empty = e.new_species(-1.0, 4096, 64)
-    e.load_maxwellian(sp, ppc, 1, -1.0 / ppc, (0.2, 0.0, 0.0), vth)
-    p = e.get_particles(sp)                                  # the loader sets no tags: give every particle its own
-    p["tag"] = np.arange(np_, dtype=np.int64) + 1
-    e.set_particles(sp, p)
-    del p
-    e.load_interpolator()
-    e.sort_p(sp)
-    assert e.species_order(sp) == "tile"
+
+    def tag(e, sp):                                          # the loader sets no tags: give every particle its own, in the loader's order
+        p = e.get_particles(sp)
+        p["tag"] = np.arange(np_, dtype=np.int64) + 1
+        e.set_particles(sp, p)
+
+    V, e, sp, empty, stream = T.species(args, before_sort=tag)
     # the edge of the energetic 1 %: from the 1-D ke histogram on the device
     ke_axis = [("ke", 0.0, 0.05 / 4096, 4096)]
     h = e.distribution(sp, ke_axis)
@@ -71,69 +51,38 @@ def main():
     if args.only is not None:
         sel = {k: d for k, d in sel.items() if k == name_a or k.split()[0] in args.only.split(",")}
     counts = {k: e.select_count(sp, **{a: b for a, b in d.items() if a not in ("fields", "index")}) for k, d in sel.items()}
-    stream = torch.cuda.ExternalStream(e.stream(), device=torch.device("cuda", 0))
-
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0 = time.perf_counter()
-        a.record(stream)
-        out = fn()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b), (time.perf_counter() - t0) * 1e3, out
-
     def calls(s):
         c = {k: (lambda d=d, k=k: e.select(s, cap=counts[k], **d)) for k, d in sel.items()}     # (cap given: one call, no counting call first)
         c["a0 select_count of (a)"] = lambda: e.select_count(s, **sel[name_a])
         c["d ke distribution, 4096 bins"] = lambda: e.distribution(s, ke_axis)
         return c
 
-    full, hollow = calls(sp), calls(empty)
-    for group in (full, hollow):                             # warm-up: code objects, the buffers grown to their size
-        for fn in group.values():
-            for _ in range(3):
-                fn()
-    ms = {k: [] for k in full}
-    ms0 = {k: [] for k in full}
-    for _ in range(args.reps):                               # alternating
-        for k in full:
-            ms[k].append(timed(full[k])[:2])
-            ms0[k].append(timed(hollow[k])[:2])
+    full = calls(sp)
+    ms, ms0 = T.alternate(stream, args.reps, full, calls(empty))
     stats = {}
     for k in sel:
         r = full[k]()
         stats[k] = (e.select_stats(), r)
     route_e, same = [], None
     if not args.no_route_e:
-        want = stats[name_a][1]
-        for _ in range(3):
-            t0 = time.perf_counter()
-            p = e.get_particles(sp)
-            t1 = time.perf_counter()
+        def mask(p):
             u = [p[c].astype(np.float64) for c in ("ux", "uy", "uz")]
-            ke = np.sqrt(((1.0 + u[0] * u[0]) + u[1] * u[1]) + u[2] * u[2]) - 1.0
-            kept = p[ke >= edge]
-            route_e.append(((t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3))
+            return p[np.sqrt(((1.0 + u[0] * u[0]) + u[1] * u[1]) + u[2] * u[2]) - 1.0 >= edge]
+        want = stats[name_a][1]
+        route_e, kept = T.host_route(e, sp, 3, mask)
         same = (len(kept), want.count, kept.tobytes() == want.particles.tobytes())
-        del p
     e.close()
 
-    lines = [f"selected particles of one species: {n}^3 cells x {ppc} per cell = {np_} particles, tile order, tags 1..np, {args.reps} alternating repeats",
-             f"device: {torch.cuda.get_device_name(0)}",
-             "milliseconds per call: median [min .. max] between events on the engine's stream; (median of the host clock around the call);",
-             "  less empty: that median minus the median of the same call on an empty species (the same clearing, waits and copies of statistics,",
-             "  no launch); for a selection it still holds the copy of the records to the host"]
-    med, kern = {}, {}
-    for k, v in ms.items():
-        ev, host = np.array([x[0] for x in v]), np.array([x[1] for x in v])
-        ev0 = np.array([x[0] for x in ms0[k]])
-        med[k], kern[k] = float(np.median(ev)), float(np.median(ev) - np.median(ev0))
-        extra = ""
-        if k in stats:
-            s, r = stats[k]
-            per = 48 + (32 if r.fields is not None else 0)
-            extra = f"  seen {s[0]} kept {s[1]} ({100.0 * s[1] / max(s[0], 1):.2f} %) written {s[2]} chunks {s[3]}; {s[2] * per / 1e6:.1f} MB to the host"
-        lines.append(f"  ({k}): {np.median(ev):.3f} [{ev.min():.3f} .. {ev.max():.3f}]  (host {np.median(host):.3f})  empty {np.median(ev0):.3f}  less empty {kern[k]:.3f}{extra}")
+    lines = T.header("selected particles", args, "tags 1..np, ")
+    lines += ["milliseconds per call: median [min .. max] between events on the engine's stream; (median of the host clock around the call);",
+              "  less empty: that median minus the median of the same call on an empty species (the same clearing, waits and copies of statistics,",
+              "  no launch); for a selection it still holds the copy of the records to the host"]
+    extras = {}
+    for k, (s, r) in stats.items():
+        per = 48 + (32 if r.fields is not None else 0)
+        extras[k] = f"  seen {s[0]} kept {s[1]} ({100.0 * s[1] / max(s[0], 1):.2f} %) written {s[2]} chunks {s[3]}; {s[2] * per / 1e6:.1f} MB to the host"
+    more, med, kern = T.call_lines(ms, ms0, "less empty", extras)
+    lines += more
     if route_e:
         total = float(np.median([c[0] + c[1] for c in route_e]))
         lines.append(f"  (e get_particles + numpy mask for (a), 3 repeats): download {np.median([c[0] for c in route_e]):.0f} ms + numpy {np.median([c[1] for c in route_e]):.0f} ms;"
@@ -144,11 +93,7 @@ def main():
                  " (expected: little more than 1, plus the copy of the records)")
     lines.append(f"bytes launch 1 of (a) reads: 16 B per particle = {16 * np_ / 1e9:.3f} GB -> {16 * np_ / k0 / 1e6:.0f} GB/s over (a0); "
                  f"(b) reads 12 B per particle (i, tag), (c) 12 B (i, dx, dz)")
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    T.finish(lines, args.out)
 
 
 if __name__ == "__main__":
