@@ -314,8 +314,8 @@ int vpic_hip_energy_bands(vpic_hip_engine_t *e, int sp, const vpic_hip_spectrum_
  * always, more than 48 bands have no window and always miss.  Misses cost time, never the result. */
 int vpic_hip_energy_spectrum_stats(vpic_hip_engine_t *e, int64_t out[2]);
 
-/* ---- phase-space distributions of a species: a 1-D or 2-D histogram over position, momentum and kinetic energy,
- * optionally of the particles inside a region, computed where the particles are (csrc/distribution.hip) ----
+/* ---- phase-space distributions of a species: a 1-D or 2-D histogram over position, momentum, kinetic energy and
+ * the coordinates in the frame of the local magnetic field, optionally of the particles inside a region, computed where the particles are (csrc/distribution.hip) ----
  * One pass over those of the species' arrays that the descriptor names (x-ux reads i, dx, ux: 12 B per particle).
  * Everything below is IEEE double, every operation rounded once, unfused.  Per live particle -- 0 <= i < nv; dead
  * slots (i = -1) are skipped, particles appended since the last sort are included:
@@ -327,6 +327,24 @@ int vpic_hip_energy_spectrum_stats(vpic_hip_engine_t *e, int64_t out[2]);
  *   UX, UY, UZ the stored float momenta promoted to double
  *   KE        sqrt(((1 + ux^2) + uy^2) + uz^2) - 1 with the promoted momenta (as vpic_hip_energy_spectrum)
  *   LOG10_KE  log10(KE); KE == 0 gives -inf, which lies in no bin
+ * In the frame of the local magnetic field (codes 16 to 21; 8 to 15 are unknown): ex, ey, ez, cbx, cby, cbz are the
+ * fields at the particle exactly as vpic_hip_species_select below states them -- float, every operation rounded once,
+ * unfused, from the interpolator AS IT IS LOADED at the call, of the particle's voxel (a particle in a ghost voxel uses
+ * that voxel's record) -- then promoted to double as Ex, Ey, Ez, Bx, By, Bz; ux, uy, uz are promoted as for UX..UZ.
+ * Everything after that is IEEE double, every operation rounded once, unfused, summed from the left:
+ *     b2    = (Bx*Bx + By*By) + Bz*Bz          B     = sqrt(b2)
+ *     udotb = (ux*Bx + uy*By) + uz*Bz          U_PAR = udotb / B
+ *     u2    = (ux*ux + uy*uy) + uz*uz
+ *     perp2 = u2 - U_PAR*U_PAR                 p2    = perp2 < 0 ? 0.0 : perp2      (a NaN stays a NaN)
+ *     U_PERP = sqrt(p2)
+ *     PITCH  = U_PAR / sqrt(u2)                (the cosine of the pitch angle)
+ *     MU     = p2 / (2.0 * B)                  (u_perp^2 / 2|cB|: the magnetic moment per unit mass, in code units)
+ *     E_PAR  = ((Ex*Bx + Ey*By) + Ez*Bz) / B
+ *   No special cases, the quotients produce the edge values: B == 0 gives B = 0 and NaN for the other five; u == 0 gives
+ *   U_PAR = U_PERP = MU = 0 and PITCH = NaN.  A NaN lies in no bin and in no range.  The momenta are the stored ones
+ *   (time-centring is the caller's business: vpic_hip_center_p first, as for a particle dump); cB is in the units the
+ *   field array holds.  A descriptor that names one of the six reads, beside the particle arrays, 24 bytes of the
+ *   voxel's interpolator record per live particle (all 72 with E_PAR); one that names none reads what it always read.
  * Selection: the particle is kept when lo <= c < hi holds for every one of the n_sel ranges (0 to 4 of them).
  * Bin: per axis t = (c - lo) / d; a kept particle is counted when t >= 0 && t < n on every axis (so a NaN is never
  * counted), in bin (int)t.  Nothing is clamped into the end bins.  counts[b1 * n0 + b0], n1 = 1 when n_axes == 1.
@@ -334,7 +352,9 @@ int vpic_hip_energy_spectrum_stats(vpic_hip_engine_t *e, int64_t out[2]);
  * bit for bit whatever order the array is in and whichever kernel pushed it. */
 enum { VPIC_HIP_COORD_X = 0, VPIC_HIP_COORD_Y, VPIC_HIP_COORD_Z,
        VPIC_HIP_COORD_UX, VPIC_HIP_COORD_UY, VPIC_HIP_COORD_UZ,
-       VPIC_HIP_COORD_KE, VPIC_HIP_COORD_LOG10_KE };
+       VPIC_HIP_COORD_KE, VPIC_HIP_COORD_LOG10_KE,                                            /* 0..7 */
+       VPIC_HIP_COORD_U_PAR = 16, VPIC_HIP_COORD_U_PERP, VPIC_HIP_COORD_PITCH, VPIC_HIP_COORD_MU,
+       VPIC_HIP_COORD_B, VPIC_HIP_COORD_E_PAR };                                              /* 16..21 */
 typedef struct { int32_t coord, n; double lo, d; } vpic_hip_dist_axis_t;        /* n bins of width d from lo */
 typedef struct { int32_t coord, pad; double lo, hi; } vpic_hip_dist_range_t;    /* keep particles with lo <= c < hi */
 typedef struct {
@@ -375,7 +395,8 @@ int vpic_hip_species_distribution_stats(vpic_hip_engine_t *e, int64_t out[4]);
  * arrays where the particles are, so that only they come to the host (csrc/select.hip) ----
  * Live particles: 0 <= i < nv; dead slots (i = -1) are skipped, particles appended since the last sort are included.
  * Coordinates and ranges are exactly those of vpic_hip_species_distribution above: IEEE double, every operation
- *   rounded once, unfused; a particle is inside a range when lo <= c < hi, so a NaN is never kept.
+ *   rounded once, unfused; a particle is inside a range when lo <= c < hi, so a NaN is never kept.  The six
+ *   coordinates in the frame of the local field are ranges like the others, from the same interpolator as `fields`.
  * Tags: `tag` is the particle's FIRST tag (vpic_particle_t::tag).  A species whose tag arrays were never allocated
  *   (no non-zero tag was ever uploaded) behaves as if every tag were 0, and the call allocates nothing for it.
  *     VPIC_HIP_SELECT_TAG_RANGE  keep when tag_lo <= tag < tag_hi

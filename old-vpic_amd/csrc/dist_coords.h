@@ -9,28 +9,44 @@ namespace vpichip {
 
 // bit c of a `need` mask: coordinate c is used by an axis or a range
 constexpr unsigned NEED_POS = 7u, NEED_KE = 3u << VPIC_HIP_COORD_KE;
+// The coordinates in the frame of the local magnetic field (U_PAR .. E_PAR).  Every one of them needs B at the particle,
+// and with it the three offsets (not the voxel's decode: that stays with X, Y, Z); E_PAR alone needs E; all but B and
+// E_PAR need the momenta.  They run in kernel instances of their own (FIELDS): a descriptor without them runs the code
+// it always ran.
+constexpr unsigned NEED_FIELD = 0x3fu << VPIC_HIP_COORD_U_PAR, NEED_FIELD_E = 1u << VPIC_HIP_COORD_E_PAR;
+constexpr unsigned NEED_FIELD_U = NEED_FIELD & ~(1u << VPIC_HIP_COORD_B | NEED_FIELD_E);
+constexpr unsigned NEED_FIELD_PERP = 1u << VPIC_HIP_COORD_U_PERP | 1u << VPIC_HIP_COORD_MU;
+static_assert(VPIC_HIP_COORD_U_PAR == 16 && VPIC_HIP_COORD_E_PAR == 21 && NEED_FIELD == 0x3f0000u, "the field coordinates are bits 16 to 21");
 
-struct DistCoords { double x, y, z, ux, uy, uz, ke, log_ke; };
+struct DistCoords { double x, y, z, ux, uy, uz, ke, log_ke, u_par, u_perp, pitch, mu, b, e_par; };
 
 // a select chain: the coordinate number is uniform, the values stay in registers
+template <bool FIELDS>
 __device__ __forceinline__ double dist_coord(const DistCoords &v, int coord) {
+  if (FIELDS) {
+    if (coord >= VPIC_HIP_COORD_U_PAR)
+      return coord == VPIC_HIP_COORD_U_PAR ? v.u_par : coord == VPIC_HIP_COORD_U_PERP ? v.u_perp : coord == VPIC_HIP_COORD_PITCH ? v.pitch
+           : coord == VPIC_HIP_COORD_MU ? v.mu : coord == VPIC_HIP_COORD_B ? v.b : v.e_par;
+  }
   return coord == VPIC_HIP_COORD_X ? v.x : coord == VPIC_HIP_COORD_Y ? v.y : coord == VPIC_HIP_COORD_Z ? v.z
        : coord == VPIC_HIP_COORD_UX ? v.ux : coord == VPIC_HIP_COORD_UY ? v.uy : coord == VPIC_HIP_COORD_UZ ? v.uz
        : coord == VPIC_HIP_COORD_KE ? v.ke : v.log_ke;
 }
 
+template <bool FIELDS>
 __device__ __forceinline__ bool dist_in_range(const DistCoords &v, const vpic_hip_dist_range_t &r) {
-  const double c = dist_coord(v, r.coord);
+  const double c = dist_coord<FIELDS>(v, r.coord);
   return c >= r.lo && c < r.hi;
 }
 
 // lo <= c < hi for every one of the n_sel ranges (0 to 4; a NaN is in no range)
+template <bool FIELDS>
 __device__ __forceinline__ bool dist_in_ranges(const DistCoords &v, const vpic_hip_dist_range_t (&sel)[4], int n_sel) {
   bool in = true;
-  if (n_sel > 0) in = in && dist_in_range(v, sel[0]);
-  if (n_sel > 1) in = in && dist_in_range(v, sel[1]);
-  if (n_sel > 2) in = in && dist_in_range(v, sel[2]);
-  if (n_sel > 3) in = in && dist_in_range(v, sel[3]);
+  if (n_sel > 0) in = in && dist_in_range<FIELDS>(v, sel[0]);
+  if (n_sel > 1) in = in && dist_in_range<FIELDS>(v, sel[1]);
+  if (n_sel > 2) in = in && dist_in_range<FIELDS>(v, sel[2]);
+  if (n_sel > 3) in = in && dist_in_range<FIELDS>(v, sel[3]);
   return in;
 }
 
@@ -39,23 +55,45 @@ struct DistRaw { int voxel; float dx, dy, dz, ux, uy, uz; };
 
 // The loads of a pass do not wait for one another (a dead slot's other words are read and not used), and the main loops
 // ask for the next pass's before they work on this one's.
+template <bool FIELDS>
 __device__ __forceinline__ DistRaw dist_load(const ParticlesK &p, long long idx, long long end, unsigned need) {
   DistRaw r{-1, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const bool u = FIELDS && (need & NEED_FIELD_U);
   if (idx < end) {
     r.voxel = p.i[idx];
-    if (need & 1u) r.dx = p.dx[idx];
-    if (need & 2u) r.dy = p.dy[idx];
-    if (need & 4u) r.dz = p.dz[idx];
-    if (need & (NEED_KE | 1u << VPIC_HIP_COORD_UX)) r.ux = p.ux[idx];
-    if (need & (NEED_KE | 1u << VPIC_HIP_COORD_UY)) r.uy = p.uy[idx];
-    if (need & (NEED_KE | 1u << VPIC_HIP_COORD_UZ)) r.uz = p.uz[idx];
+    if (FIELDS || (need & 1u)) r.dx = p.dx[idx];
+    if (FIELDS || (need & 2u)) r.dy = p.dy[idx];
+    if (FIELDS || (need & 4u)) r.dz = p.dz[idx];
+    if (u || (need & (NEED_KE | 1u << VPIC_HIP_COORD_UX))) r.ux = p.ux[idx];
+    if (u || (need & (NEED_KE | 1u << VPIC_HIP_COORD_UY))) r.uy = p.uy[idx];
+    if (u || (need & (NEED_KE | 1u << VPIC_HIP_COORD_UZ))) r.uz = p.uz[idx];
   }
   return r;
 }
 
+// What a FIELDS instance reads of the interpolator record of the particle's voxel: the 24 bytes of B always, the 48 of
+// E only when E_PAR is named.
+struct DistField { float4 b; float2 c; float4 ex, ey, ez; };   // {cbx, dcbxdx, cby, dcbydy}, {cbz, dcbzdz}, {ex, dexdy, dexdz, d2exdydz}, ...
+
+// The gather of one pass.  Only a live lane (0 <= voxel < nv) forms an address: a dead slot, a lane behind the end of
+// its chunk (voxel -1) and i >= nv read nothing.  The main loops issue it one pass ahead, as soon as that pass's
+// voxels have arrived and before the arithmetic of the pass in hand.
+__device__ __forceinline__ DistField dist_gather(const vpic_interpolator_t *__restrict__ fi, int voxel, int nv, unsigned need) {
+  DistField f{};
+  if (voxel >= 0 && voxel < nv) {
+    const float4 *q = reinterpret_cast<const float4 *>(fi + voxel);
+    f.b = q[3];
+    f.c = *reinterpret_cast<const float2 *>(q + 4);
+    if (need & NEED_FIELD_E) { f.ex = q[0]; f.ey = q[1]; f.ez = q[2]; }
+  }
+  return f;
+}
+static_assert(sizeof(vpic_interpolator_t) == 80, "an interpolator record is five float4");
+
 // The coordinates that `need` names of a LIVE particle (0 <= r.voxel < nv); cx, cy, cz: the decoded voxel, ghost layer
-// included (set when a position is needed, otherwise left alone).
-__device__ __forceinline__ DistCoords dist_coords(const DistRaw &r, unsigned need, const TileK &t, int &cx, int &cy, int &cz) {
+// included (set when a position is needed, otherwise left alone).  f: its voxel's record (FIELDS instances only).
+template <bool FIELDS>
+__device__ __forceinline__ DistCoords dist_coords(const DistRaw &r, const DistField &f, unsigned need, const TileK &t, int &cx, int &cy, int &cz) {
   DistCoords v{};
   if (need & NEED_POS) {
     voxel_cell(r.voxel, t, cx, cy, cz);
@@ -68,6 +106,31 @@ __device__ __forceinline__ DistCoords dist_coords(const DistRaw &r, unsigned nee
     // as spectrum.hip: summed from the left
     v.ke = sqrt(((1.0 + v.ux * v.ux) + v.uy * v.uy) + v.uz * v.uz) - 1.0;
     if (need & 1u << VPIC_HIP_COORD_LOG10_KE) v.log_ke = log10(v.ke);
+  }
+  if (FIELDS) {
+    // the fields at the particle as select_write_kernel forms them (float, unfused), then double, summed from the left;
+    // no special case: B == 0 and u == 0 give what the quotients give
+    const double bx = (double)(f.b.x + r.dx * f.b.y), by = (double)(f.b.z + r.dy * f.b.w), bz = (double)(f.c.x + r.dz * f.c.y);
+    const double b = sqrt((bx * bx + by * by) + bz * bz);
+    v.b = b;
+    if (need & NEED_FIELD_U) {
+      const double u_par = ((v.ux * bx + v.uy * by) + v.uz * bz) / b;
+      const double u2 = (v.ux * v.ux + v.uy * v.uy) + v.uz * v.uz;
+      v.u_par = u_par;
+      if (need & NEED_FIELD_PERP) {
+        const double perp2 = u2 - u_par * u_par;
+        const double p2 = perp2 < 0.0 ? 0.0 : perp2;                            // (a NaN stays a NaN)
+        if (need & 1u << VPIC_HIP_COORD_U_PERP) v.u_perp = sqrt(p2);
+        if (need & 1u << VPIC_HIP_COORD_MU) v.mu = p2 / (2.0 * b);
+      }
+      if (need & 1u << VPIC_HIP_COORD_PITCH) v.pitch = u_par / sqrt(u2);
+    }
+    if (need & NEED_FIELD_E) {
+      const float ex = (f.ex.x + r.dy * f.ex.y) + r.dz * (f.ex.z + r.dy * f.ex.w);
+      const float ey = (f.ey.x + r.dz * f.ey.y) + r.dx * (f.ey.z + r.dz * f.ey.w);
+      const float ez = (f.ez.x + r.dx * f.ez.y) + r.dy * (f.ez.z + r.dx * f.ez.w);
+      v.e_par = (((double)ex * bx + (double)ey * by) + (double)ez * bz) / b;
+    }
   }
   return v;
 }

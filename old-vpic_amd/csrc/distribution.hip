@@ -1,5 +1,5 @@
-// distribution.hip -- a 1-D or 2-D histogram of one species over position, momentum and kinetic energy, optionally of
-// the particles inside a region (vpic_hip_species_distribution; include/vpic_hip.h states the arithmetic).  One
+// distribution.hip -- a 1-D or 2-D histogram of one species over position, momentum, kinetic energy and the coordinates
+// in the frame of the local magnetic field (u_par, u_perp, pitch, mu, |cB|, E_par), optionally of the particles inside a region (vpic_hip_species_distribution; include/vpic_hip.h states the arithmetic).  One
 // streaming pass over those SoA arrays the descriptor names (x-ux: i, dx, ux, 12 B per particle).  Every counter is
 // an integer: the result does not depend on the order of the array nor on which kernel instance pushed it.
 // Which path a descriptor takes, the window's shape and how tiles are dealt to wavefronts are host decisions in policy.h
@@ -70,10 +70,15 @@ __device__ __forceinline__ void flush_dist_window(unsigned *win, int base, const
 //     and is counted as a miss (the protocol: engine.h, window_add).
 //   DIST_GLOBAL: every counted particle adds to counts[] and is counted as a miss.
 // stats: live particles seen, kept by the selection, counted, misses.
-template <int PATH>
+// FIELDS: the descriptor names a coordinate in the frame of the local field (dist_coords.h); every path, the walk by
+//   tile and the statistics are the same.  The particle loads then run TWO passes ahead and the gather of the
+//   interpolator record one: pass n + 1's gather is issued at the top of pass n, when its voxels (asked for a pass ago)
+//   have arrived, so that it is in flight during pass n's arithmetic as the particle loads are.  fi is not read otherwise.
+template <int PATH, bool FIELDS>
 __global__ __launch_bounds__(64 * DIST_WAVES)
 void species_distribution_kernel(ParticlesK p, long long np, long long chunk, DistK k, DistTiles tl, GridK g, TileK t,
-                                 unsigned long long *__restrict__ counts, unsigned long long *__restrict__ stats) {
+                                 unsigned long long *__restrict__ counts, unsigned long long *__restrict__ stats,
+                                 const vpic_interpolator_t *__restrict__ fi) {
   extern __shared__ unsigned s_dist[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lds_words = PATH == DIST_LDS ? k.n0 * k.n1 : PATH == DIST_WINDOW ? DIST_WAVES * k.win * k.n_other : 0;
@@ -118,10 +123,22 @@ void species_distribution_kernel(ParticlesK p, long long np, long long chunk, Di
     begin = tl.tpart[(size_t)tile * TILE_CELLS];
     end = tile + 1 < t.ntiles ? (long long)tl.tpart[(size_t)(tile + 1) * TILE_CELLS] : tl.n_sorted;
   }
-  DistRaw next = dist_load(p, begin + lane, end, k.need);
+  DistRaw next = dist_load<FIELDS>(p, begin + lane, end, k.need), next2{};
+  DistField f{}, f_next{};
+  if (FIELDS) {
+    next2 = dist_load<FIELDS>(p, begin + 64 + lane, end, k.need);
+    f_next = dist_gather(fi, next.voxel, g.nv, k.need);
+  }
   for (long long at = begin; at < end; at += 64) {
     const DistRaw r = next;
-    next = dist_load(p, at + 64 + lane, end, k.need);
+    if (FIELDS) {
+      f = f_next;
+      next = next2;
+      f_next = dist_gather(fi, next.voxel, g.nv, k.need);
+      next2 = dist_load<FIELDS>(p, at + 128 + lane, end, k.need);
+    } else {
+      next = dist_load<FIELDS>(p, at + 64 + lane, end, k.need);
+    }
     const int voxel = r.voxel;
     const bool live = voxel >= 0 && voxel < g.nv;                            // i < 0: a dead slot (engine.h, Species::n_holes)
     n_seen += __popcll(__ballot(live));
@@ -130,23 +147,23 @@ void species_distribution_kernel(ParticlesK p, long long np, long long chunk, Di
     int cell_pos = 0;                                                        // DIST_WINDOW: the particle's cell along the position axis, from 0
     if (live) {
       int cx = 0, cy = 0, cz = 0;
-      v = dist_coords(r, k.need, t, cx, cy, cz);                             // (dist_coords.h)
+      v = dist_coords<FIELDS>(r, f, k.need, t, cx, cy, cz);                            // (dist_coords.h)
       if (PATH == DIST_WINDOW) {
         const int c = k.pos_axis == 0 ? k.d.axis[0].coord : k.d.axis[1].coord;
         cell_pos = (c == VPIC_HIP_COORD_X ? cx : c == VPIC_HIP_COORD_Y ? cy : cz) - 1;
       }
     }
-    const bool kept = live && dist_in_ranges(v, k.d.sel, k.d.n_sel);
+    const bool kept = live && dist_in_ranges<FIELDS>(v, k.d.sel, k.d.n_sel);
     n_kept += __popcll(__ballot(kept));
     bool counted = kept;
     int b0 = 0, b1 = 0;
     {
-      const double t0 = (dist_coord(v, k.d.axis[0].coord) - k.d.axis[0].lo) / k.d.axis[0].d;
+      const double t0 = (dist_coord<FIELDS>(v, k.d.axis[0].coord) - k.d.axis[0].lo) / k.d.axis[0].d;
       counted = counted && t0 >= 0.0 && t0 < (double)k.n0;
       b0 = counted ? (int)t0 : 0;
     }
     if (k.d.n_axes == 2) {
-      const double t1 = (dist_coord(v, k.d.axis[1].coord) - k.d.axis[1].lo) / k.d.axis[1].d;
+      const double t1 = (dist_coord<FIELDS>(v, k.d.axis[1].coord) - k.d.axis[1].lo) / k.d.axis[1].d;
       counted = counted && t1 >= 0.0 && t1 < (double)k.n1;
       b1 = counted ? (int)t1 : 0;
     }
@@ -230,10 +247,14 @@ int k_species_distribution(Engine *e, Species &s, const vpic_hip_dist_t &d) {
         if (k_check_tile_partition(e, s, e->dist_stats.bad_partition())) return 1;
       }
     }
-    auto kernel = path == DIST_LDS ? species_distribution_kernel<DIST_LDS>
-                : path == DIST_WINDOW ? species_distribution_kernel<DIST_WINDOW> : species_distribution_kernel<DIST_GLOBAL>;
+    // a descriptor that names no field coordinate runs the instances it always ran
+    auto kernel = k.need & NEED_FIELD
+      ? (path == DIST_LDS ? species_distribution_kernel<DIST_LDS, true>
+         : path == DIST_WINDOW ? species_distribution_kernel<DIST_WINDOW, true> : species_distribution_kernel<DIST_GLOBAL, true>)
+      : (path == DIST_LDS ? species_distribution_kernel<DIST_LDS, false>
+         : path == DIST_WINDOW ? species_distribution_kernel<DIST_WINDOW, false> : species_distribution_kernel<DIST_GLOBAL, false>);
     hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(64 * DIST_WAVES), lds, e->stream, s.p, (long long)s.np, ch.chunk, k, tl, e->gk, tk,
-                       e->dist_counts, e->dist_stats.dev);
+                       e->dist_counts, e->dist_stats.dev, (const vpic_interpolator_t *)e->fi);
     VH_CHECK(hipGetLastError());
   }
   VH_CHECK(hipMemcpyAsync(e->dist_host, e->dist_counts, bins * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));

@@ -656,10 +656,14 @@ static int check_range_count(const char *what, int n_sel) {
   if (n_sel < 0 || n_sel > 4) VH_FAIL("%s: %d ranges (0 to 4)", what, n_sel);
   return 0;
 }
+// the coordinates of include/vpic_hip.h: 0 to 7 and, in the frame of the local field, 16 to 21
+static bool known_coord(int c) {
+  return (c >= VPIC_HIP_COORD_X && c <= VPIC_HIP_COORD_LOG10_KE) || (c >= VPIC_HIP_COORD_U_PAR && c <= VPIC_HIP_COORD_E_PAR);
+}
 static int check_ranges(const char *what, const vpic_hip_dist_range_t *sel, int n_sel) {
   if (check_range_count(what, n_sel)) return 1;
   for (int r = 0; r < n_sel; r++)
-    if (sel[r].coord < VPIC_HIP_COORD_X || sel[r].coord > VPIC_HIP_COORD_LOG10_KE) VH_FAIL("%s: unknown coordinate %d of range %d", what, sel[r].coord, r);
+    if (!known_coord(sel[r].coord)) VH_FAIL("%s: unknown coordinate %d of range %d", what, sel[r].coord, r);
   return 0;
 }
 static int check_spectrum(const vpic_hip_spectrum_t *s, bool need_lin) {
@@ -714,7 +718,7 @@ int vpic_hip_species_distribution(vpic_hip_engine_t *e, int sp, const vpic_hip_d
   long long bins = 1;
   for (int a = 0; a < d->n_axes; a++) {
     const vpic_hip_dist_axis_t &x = d->axis[a];
-    if (x.coord < VPIC_HIP_COORD_X || x.coord > VPIC_HIP_COORD_LOG10_KE) VH_FAIL("distribution: unknown coordinate %d of axis %d", x.coord, a);
+    if (!known_coord(x.coord)) VH_FAIL("distribution: unknown coordinate %d of axis %d", x.coord, a);
     if (x.n < 1) VH_FAIL("distribution: %d bins on axis %d", x.n, a);
     if (!(x.d > 0) || !std::isfinite(x.d)) VH_FAIL("distribution: bin width %g of axis %d", x.d, a);
     bins *= x.n;                                            // (at most 2^62)

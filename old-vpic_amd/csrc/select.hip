@@ -1,5 +1,5 @@
-// select.hip -- the particles of one species that lie inside up to four ranges over position, momentum and kinetic
-// energy and satisfy up to two conditions on their tag, gathered into dense arrays in the order of the species' array
+// select.hip -- the particles of one species that lie inside up to four ranges over position, momentum, kinetic
+// energy and the coordinates in the frame of the local magnetic field, and satisfy up to two conditions on their tag, gathered into dense arrays in the order of the species' array
 // (vpic_hip_species_select; include/vpic_hip.h states the semantics and the arithmetic).  Three launches, and kernel
 // boundaries are the only ordering between workgroups -- no workgroup ever waits for a word that another one writes:
 //   1  select_mark_kernel   streams the arrays the descriptor needs, stores one keep bit per particle and one kept
@@ -41,25 +41,40 @@ __device__ __forceinline__ bool select_tag_ok(const vpic_hip_select_t &s, long l
 // Launch 1.  Chunk c is particles [c * SEL_CHUNK, (c + 1) * SEL_CHUNK) of the array; wavefront w of the workgroup
 // takes the groups of 64 particles w, w + 4, ... of it.  MASKS: the keep masks are stored (mask[] holds SEL_GROUPS
 // words for every chunk, the last chunk's beyond np included: zero).  tag: null when every tag reads 0.
-template <bool MASKS>
+// FIELDS: a range names a coordinate in the frame of the local field (dist_coords.h).  As in distribution.hip, the
+// particle loads then run two passes ahead and the gather of the interpolator record (by live lanes only) one.
+template <bool MASKS, bool FIELDS>
 __global__ __launch_bounds__(64 * SEL_WAVES)
 void select_mark_kernel(ParticlesK p, const int64_t *__restrict__ tag, long long np, long long n_chunks, SelectK k, GridK g, TileK t,
-                        unsigned long long *__restrict__ mask, unsigned *__restrict__ counts, unsigned long long *__restrict__ stats) {
+                        unsigned long long *__restrict__ mask, unsigned *__restrict__ counts, unsigned long long *__restrict__ stats,
+                        const vpic_interpolator_t *__restrict__ fi) {
   __shared__ unsigned s_kept[SEL_WAVES];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned long long n_seen = 0;
   for (long long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
     const long long first = c * SEL_CHUNK + threadIdx.x;
     unsigned n_kept = 0;
-    DistRaw next = dist_load(p, first, np, k.need);
+    DistRaw next = dist_load<FIELDS>(p, first, np, k.need), next2{};
+    DistField f{}, f_next{};
+    if (FIELDS) {
+      next2 = dist_load<FIELDS>(p, first + 64 * SEL_WAVES, np, k.need);
+      f_next = dist_gather(fi, next.voxel, g.nv, k.need);
+    }
     long long next_tag = (k.use_tag && tag && first < np) ? tag[first] : 0;
 #pragma unroll 2
     for (int pass = 0; pass < SEL_PASSES; pass++) {
       const DistRaw r = next;
       const long long r_tag = next_tag;
+      if (FIELDS) {
+        f = f_next;
+        next = next2;
+        f_next = dist_gather(fi, next.voxel, g.nv, k.need);                    // (behind the chunk's last pass: voxel -1, nothing is read)
+        next2 = pass + 2 < SEL_PASSES ? dist_load<FIELDS>(p, first + (long long)(pass + 2) * (64 * SEL_WAVES), np, k.need)
+                                      : DistRaw{-1, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      }
       if (pass + 1 < SEL_PASSES) {
         const long long idx = first + (long long)(pass + 1) * (64 * SEL_WAVES);
-        next = dist_load(p, idx, np, k.need);
+        if (!FIELDS) next = dist_load<FIELDS>(p, idx, np, k.need);
         next_tag = (k.use_tag && tag && idx < np) ? tag[idx] : 0;
       }
       const bool live = r.voxel >= 0 && r.voxel < g.nv;                      // i < 0: a dead slot (engine.h, Species::n_holes)
@@ -68,8 +83,8 @@ void select_mark_kernel(ParticlesK p, const int64_t *__restrict__ tag, long long
       if (k.s.n_sel > 0 && __any(live)) {
         DistCoords v{};
         int cx = 0, cy = 0, cz = 0;
-        if (live) v = dist_coords(r, k.need, t, cx, cy, cz);
-        kept = live && dist_in_ranges(v, k.s.sel, k.s.n_sel);
+        if (live) v = dist_coords<FIELDS>(r, f, k.need, t, cx, cy, cz);
+        kept = live && dist_in_ranges<FIELDS>(v, k.s.sel, k.s.n_sel);
       }
       if (k.use_tag) kept = kept && select_tag_ok(k.s, r_tag);
       const unsigned long long m = __ballot(kept);
@@ -185,9 +200,11 @@ int k_species_select(Engine *e, Species &s, const vpic_hip_select_t &d, int64_t 
   const unsigned nb = (unsigned)std::min<long long>(n_chunks, SEL_MAX_BLOCKS);
   const TileK tk = make_tile_k(e->gk);
   if (n_chunks > 0) {
-    auto mark = count_only ? select_mark_kernel<false> : select_mark_kernel<true>;
+    // ranges that name no field coordinate run the instances they always ran
+    auto mark = k.need & NEED_FIELD ? (count_only ? select_mark_kernel<false, true> : select_mark_kernel<true, true>)
+                                    : (count_only ? select_mark_kernel<false, false> : select_mark_kernel<true, false>);
     hipLaunchKernelGGL(mark, dim3(nb), dim3(64 * SEL_WAVES), 0, e->stream, s.p, tag, np, n_chunks, k, e->gk, tk,
-                       count_only ? nullptr : e->sel_mask, e->sel_counts, e->sel_stats.dev);
+                       count_only ? nullptr : e->sel_mask, e->sel_counts, e->sel_stats.dev, (const vpic_interpolator_t *)e->fi);
     VH_CHECK(hipGetLastError());
     hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(256), 0, e->stream, (const unsigned *)e->sel_counts, n_chunks, e->sel_offsets, e->sel_stats.dev);
     VH_CHECK(hipGetLastError());

@@ -55,6 +55,9 @@ class DistDesc(C.Structure):
 
 assert C.sizeof(DistDesc) == 152
 DIST_COORDS = {"x": 0, "y": 1, "z": 2, "ux": 3, "uy": 4, "uz": 5, "ke": 6, "log10_ke": 7}    # VPIC_HIP_COORD_*
+# in the frame of the local magnetic field, from the interpolator as it is loaded (VPIC_HIP_COORD_U_PAR ..).  VPIC_HIP_COORD_PITCH
+# is "cos_pitch" here: it IS the cosine, and the name "pitch" stays unknown (KeyError), which callers and tests rely on.
+FIELD_COORDS = {"u_par": 16, "u_perp": 17, "cos_pitch": 18, "mu": 19, "b": 20, "e_par": 21}
 DIST_MAX_BINS, DIST_LDS_BINS = 1 << 22, 8192                                                   # VPIC_HIP_DIST_*
 
 
@@ -69,10 +72,15 @@ SELECT_TAG_RANGE, SELECT_TAG_EVERY = 1, 2                                       
 SelectResult = collections.namedtuple("SelectResult", "count particles fields index")
 
 
+def _coord(name):
+    """VPIC_HIP_COORD_* of a coordinate's name (KeyError for an unknown one)"""
+    return FIELD_COORDS[name] if name in FIELD_COORDS else DIST_COORDS[name]
+
+
 def _set_ranges(desc, select):
     """the (coord, lo, hi) ranges of `select`, coordinates by name, into desc.sel (vpic_hip_dist_range_t[4])"""
     for k, (coord, lo, hi) in enumerate(select):
-        desc.sel[k] = DistRange(DIST_COORDS[coord], 0, float(lo), float(hi))
+        desc.sel[k] = DistRange(_coord(coord), 0, float(lo), float(hi))
 
 
 def dist_desc(axes, select=()):
@@ -82,7 +90,7 @@ def dist_desc(axes, select=()):
         raise ValueError("distribution: one or two axes and at most four ranges")
     d = DistDesc(len(axes), len(select))
     for k, (coord, lo, width, n) in enumerate(axes):
-        d.axis[k] = DistAxis(DIST_COORDS[coord], int(n), float(lo), float(width))
+        d.axis[k] = DistAxis(_coord(coord), int(n), float(lo), float(width))
     _set_ranges(d, select)
     return d
 
@@ -399,7 +407,10 @@ class Engine:
     def distribution(self, sp, axes, select=()):
         """uint64[n0] or uint64[n1, n0]: the histogram of the species over one or two axes (coord, lo, d, n) -- n bins of
         width d from lo; coord one of "x", "y", "z" (cells from the low corner of the interior), "ux", "uy", "uz", "ke",
-        "log10_ke" -- of the particles inside every (coord, lo, hi) range of `select`."""
+        "log10_ke", or in the frame of the local magnetic field "u_par", "u_perp", "cos_pitch" (the cosine of the pitch angle),
+        "mu" (u_perp^2 / 2|cB|), "b" (|cB|), "e_par", which use the interpolator AS IT IS LOADED at the call
+        (load_interpolator first for the current fields) -- of the particles inside every (coord, lo, hi) range of
+        `select`, whose coordinates are the same twelve."""
         d = dist_desc(axes, select)
         n0, n1 = max(d.axis[0].n, 0), max(d.axis[1].n, 0) if d.n_axes == 2 else 1
         counts = np.zeros(min(n0 * n1, DIST_MAX_BINS), np.uint64)        # (a descriptor the library refuses is refused below)
@@ -415,7 +426,9 @@ class Engine:
     # ---- selected particles (include/vpic_hip.h: vpic_hip_species_select) ----
     def select_count(self, sp, select=(), tag_range=None, tag_every=None):
         """how many live particles of the species lie inside every (coord, lo, hi) range of `select` and have the tags
-        asked for: tag_range = (lo, hi) keeps lo <= tag < hi, tag_every = (every, phase) keeps tag % every == phase."""
+        asked for: tag_range = (lo, hi) keeps lo <= tag < hi, tag_every = (every, phase) keeps tag % every == phase.
+        The coordinates are those of `distribution`, "u_par", "u_perp", "cos_pitch", "mu", "b" and "e_par" included, which
+        use the interpolator as it is loaded at the call."""
         d = select_desc(select, tag_range, tag_every)
         n = C.c_int64()
         self._ck(self._l.vpic_hip_species_select_count(self._h, int(sp), C.byref(d), C.byref(n)))
@@ -426,7 +439,8 @@ class Engine:
         particles particle_t[n]; fields float32[n, 6], (ex, ey, ez, cbx, cby, cbz) at the particle from the interpolator
         as it is loaded, or None; index int64[n], the particle's place in the array, or None.  n = count, or
         min(count, cap) when a cap is given (count is the number kept either way); without one the particles are counted
-        first and the arrays sized exactly."""
+        first and the arrays sized exactly.  A range over "u_par", "u_perp", "cos_pitch", "mu", "b" or "e_par" uses the same
+        interpolator as `fields` does: the one loaded at the call."""
         d = select_desc(select, tag_range, tag_every)
         if cap is None:
             cap = self.select_count(sp, select, tag_range, tag_every)

@@ -311,6 +311,10 @@ public:
   // (lo - grid->x0) / grid->dx and d / grid->dx, in double.  counts[] holds this rank's particles only: every rank bins
   // against the same physical edges and integer counts add exactly, so a deck on several ranks sums them (as energy.cxx
   // does with its own).  The particle mirror does not become resident.  Only once the run has started.
+  // The coordinates in the frame of the local magnetic field -- VPIC_HIP_COORD_U_PAR, _U_PERP, _PITCH, _MU, _B, _E_PAR, as
+  // axes and as ranges, here and in select_particles -- are passed through untouched (they have no physical-unit form:
+  // momenta are u, cB and E are in the units the field array holds).  They use the interpolator on the device, which
+  // advance() has loaded for the current fields when user_diagnostics runs, and the stored momenta.
   void distribution(species_t *sp, const vpic_hip_dist_t *d, uint64_t *counts);
   // The particles of a species inside up to four ranges and with the tags asked for, from the resident state, in place of
   // a loop over sp->p that tests every particle (vpic_hip_species_select, include/vpic_hip.h: the descriptor, the order,

@@ -49,6 +49,21 @@ def species(args, before_sort=None):
     return V, e, sp, empty, torch.cuda.ExternalStream(e.stream(), device=torch.device("cuda", 0))
 
 
+def set_field(V, e, cells, seed=4):
+    """A magnetic and an electric field for the coordinates in the frame of the local field (the species above is loaded
+    in vacuum, where every one of them is NaN): a guide field of 0.5 along x plus seeded values in every voxel and
+    component of the interpolator, set as loaded.  What a pass costs does not depend on the values."""
+    nv = (cells + 2) ** 3
+    rng = np.random.default_rng(seed)
+    fi = np.zeros(nv, V.layout.interpolator_t)
+    for name in fi.dtype.names:
+        if name != "_pad":
+            fi[name] = rng.uniform(-0.25, 0.25, nv).astype(np.float32)
+    fi["cbx"] += np.float32(0.5)
+    e.set_interpolator(fi)
+    return fi
+
+
 def timed(stream, fn):
     """(ms between events on the stream around fn(), ms of the host clock around it, what fn returned)"""
     import torch

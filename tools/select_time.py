@@ -6,6 +6,8 @@ with tags 1..np -- the state profiles/distribution_time.txt used, plus the tags 
   (c)  a box of 1/16 of the domain (a quarter of x by a quarter of z), particles only
   (cf) the same with fields and index
   (a0) select_count of (a): launches 1 and 2 alone
+  (p0) select_count of 0.9 <= pitch < 1, in the frame of the local field (i, the offsets, the momenta and 24 B of the voxel's
+       interpolator record, which holds a guide field plus seeded values: diag_timing.set_field): its neighbour is (a0)
   (d)  the 1-D ke distribution over the same species (i, ux, uy, uz: the bytes launch 1 of (a) reads): the yardstick
   (e)  get_particles + a numpy mask: the only route there was, for (a)
 (a) to (d) alternate.  Every call is timed with the host clock, and with events on the engine's stream around it; the
@@ -26,7 +28,9 @@ def main():
     ap.add_argument("--no-route-e", action="store_true", help="leave (e) out (runs under a profiler)")
     ap.add_argument("--only", default=None, help="selections to run beside (a), (a0) and (d), e.g. 'b' or 'c,cf' or '' (so that a kernel trace's "
                                                  "per-kernel averages are those of one selection)")
+    ap.add_argument("--box-frame-only", action="store_true", help="leave (p0) out: a library from before the field-frame coordinates (VPIC_HIP_LIB)")
     args = ap.parse_args()
+    field = not args.box_frame_only
     n, ppc = args.cells, args.ppc
     np_ = n ** 3 * ppc
 
@@ -36,6 +40,7 @@ def main():
         e.set_particles(sp, p)
 
     V, e, sp, empty, stream = T.species(args, before_sort=tag)
+    T.set_field(V, e, n)
     # the edge of the energetic 1 %: from the 1-D ke histogram on the device
     ke_axis = [("ke", 0.0, 0.05 / 4096, 4096)]
     h = e.distribution(sp, ke_axis)
@@ -54,6 +59,8 @@ def main():
     def calls(s):
         c = {k: (lambda d=d, k=k: e.select(s, cap=counts[k], **d)) for k, d in sel.items()}     # (cap given: one call, no counting call first)
         c["a0 select_count of (a)"] = lambda: e.select_count(s, **sel[name_a])
+        if field:
+            c["p0 select_count of 0.9 <= pitch < 1"] = lambda: e.select_count(s, select=[("cos_pitch", 0.9, 1.0)])
         c["d ke distribution, 4096 bins"] = lambda: e.distribution(s, ke_axis)
         return c
 
@@ -71,6 +78,7 @@ def main():
         want = stats[name_a][1]
         route_e, kept = T.host_route(e, sp, 3, mask)
         same = (len(kept), want.count, kept.tobytes() == want.particles.tobytes())
+    e_pitch = e.select_count(sp, select=[("cos_pitch", 0.9, 1.0)]) if field else 0
     e.close()
 
     lines = T.header("selected particles", args, "tags 1..np, ")
@@ -93,6 +101,10 @@ def main():
                  " (expected: little more than 1, plus the copy of the records)")
     lines.append(f"bytes launch 1 of (a) reads: 16 B per particle = {16 * np_ / 1e9:.3f} GB -> {16 * np_ / k0 / 1e6:.0f} GB/s over (a0); "
                  f"(b) reads 12 B per particle (i, tag), (c) 12 B (i, dx, dz)")
+    if not field:
+        return T.finish(lines, args.out)
+    kp = kern["p0 select_count of 0.9 <= pitch < 1"]
+    lines.append(f"in the frame of the local field: (p0) / (a0) = {kp / k0:.2f}; (p0) keeps {e_pitch} of {np_}  (nothing was fixed in advance; above 2: say where the time goes)")
     T.finish(lines, args.out)
 
 
