@@ -561,6 +561,36 @@ int vpic_hip_accumulate_hydro_p(vpic_hip_engine_t *e, int sp);       /* species_
  * global memory (appended since the sort, drifted out of their tile's window, or a species that is not in tile order), out[3]
  * contributions outside the fixed-point range of the deterministic mode (vpic_hip_set_accumulation).  Waits for the stream. */
 int vpic_hip_moments_stats(vpic_hip_engine_t *e, int64_t out[4]);
+/* ---- the hydro moments of a SELECTION of a species: what accumulate_hydro_p does -- the same arithmetic per particle
+ * (csrc/moments_device.h), the same engine-owned hydro array -- where only the particles add that
+ * vpic_hip_species_select would return for the same descriptor and species at that moment (csrc/moments.hip) ----
+ * Which particles are kept: a particle is kept when every one of the n_sel ranges holds (lo <= c < hi; a NaN is in no
+ *   range) and every enabled tag condition holds.  The coordinates are those of vpic_hip_species_distribution, bit for
+ *   bit: the same double arithmetic, the six in the frame of the local field included.  The fields at the particle come
+ *   from the interpolator AS IT IS LOADED at the call.  A species whose tag arrays were never allocated behaves as if
+ *   every tag were 0, as for vpic_hip_species_select.
+ * Momenta: the coordinates use the STORED momenta, as every other selection does; the moments use the momenta advanced
+ *   by half a step, as hydro_p.c does.  A caller who wants both at the same time level runs vpic_hip_center_p first, as
+ *   for a particle dump.
+ * Voxels at the top of the array: accumulate_hydro_p skips particles in the ghost voxels at the top of the array
+ *   (i >= nv - (nx+2)(ny+2) - (nx+2) - 1: the 8 nodes of such a cell are not all inside the array); they stay skipped.
+ * Order and ownership: the species is read and left as it is; the call never sorts or reorders it, not even in
+ *   deterministic mode.  A species in tile order whose partition is valid and that has no pending movers is summed by the
+ *   tile pass plus the tail pass; any other goes through the per-particle pass over the whole array (in float mode too:
+ *   never the by-cell route, which sorts by voxel).
+ * Deterministic mode (vpic_hip_set_accumulation): the fixed-point scale is that of the whole-species call -- from the
+ *   species' largest |q|, not from the kept particles -- so the sums are bit-identical to those of accumulate_hydro_p on
+ *   a species of the same q_m and largest |q| that holds exactly the kept particles.  The same refusal applies to
+ *   contributions out of range: nothing is added and an error is returned.
+ * vpic_hip_moments_stats after this call: out[0] particles kept and summed, out[1] of them added through LDS, out[2]
+ *   through global memory (out[1] + out[2] == out[0]), out[3] contributions out of the fixed-point range.  out[0] equals
+ *   what vpic_hip_species_select_count returns for the same descriptor, except for kept particles in the skipped ghost
+ *   voxels at the top of the array, which select counts and this call does not sum.
+ * A chargeless species (tracer copies) adds nothing, as in accumulate_hydro_p.
+ * Fails (non-zero, vpic_hip_last_error) on a bad sp, a NULL s, n_sel outside 0..4, an unknown coordinate, unknown flag
+ * bits, (TAG_EVERY) tag_every < 1 or tag_phase outside [0, tag_every): the checks of vpic_hip_species_select.  The
+ * hydro array is then unchanged.  There is no accumulate_rho_p twin: rho of the selection is moment 3 of the array. */
+int vpic_hip_accumulate_hydro_p_select(vpic_hip_engine_t *e, int sp, const vpic_hip_select_t *s);
 int vpic_hip_synchronize_hydro(vpic_hip_engine_t *e);                /* sf_interface/hydro.c:28-163: local adjustment + faces shared with itself */
 int vpic_hip_local_adjust_hydro(vpic_hip_engine_t *e);               /* sf_interface/hydro.c:165-200 */
 int vpic_hip_synchronize_hydro_self(vpic_hip_engine_t *e, int axis);

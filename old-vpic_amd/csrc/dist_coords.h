@@ -1,6 +1,7 @@
 // dist_coords.h -- the coordinates of a particle and the ranges over them (include/vpic_hip.h states the arithmetic:
 // IEEE double, every operation rounded once, unfused), shared by the diagnostics that take a vpic_hip_dist_range_t --
-// the histograms of distribution.hip and the selection of select.hip -- so that the two cannot drift apart.
+// the histograms of distribution.hip, the selection of select.hip and the selected moments of moments.hip -- so that they
+// cannot drift apart.
 #pragma once
 #include "engine.h"
 #include <math.h>
@@ -133,6 +134,34 @@ __device__ __forceinline__ DistCoords dist_coords(const DistRaw &r, const DistFi
     }
   }
   return v;
+}
+
+// ---- a whole selection (vpic_hip_select_t): the ranges and the tag conditions, for select.hip and the selected moments of
+// moments.hip ----
+struct SelectK {
+  vpic_hip_select_t s;
+  unsigned need;                                           // as DistK::need: the coordinates the ranges name
+  int use_tag;                                             // a tag condition is enabled (the flags of s)
+};
+// (host) of a checked descriptor
+inline SelectK make_select_k(const vpic_hip_select_t &d) {
+  SelectK k{};
+  k.s = d;
+  for (int r = 0; r < d.n_sel; r++) k.need |= 1u << d.sel[r].coord;
+  k.use_tag = (d.flags & (VPIC_HIP_SELECT_TAG_RANGE | VPIC_HIP_SELECT_TAG_EVERY)) != 0;
+  return k;
+}
+
+// the tag conditions of a descriptor (all enabled ones must hold)
+__device__ __forceinline__ bool select_tag_ok(const vpic_hip_select_t &s, long long tag) {
+  bool ok = true;
+  if (s.flags & VPIC_HIP_SELECT_TAG_RANGE) ok = ok && tag >= s.tag_lo && tag < s.tag_hi;
+  if (s.flags & VPIC_HIP_SELECT_TAG_EVERY) {
+    long long r = tag % s.tag_every;                       // (|r| < every: r + every cannot overflow)
+    if (r < 0) r += s.tag_every;
+    ok = ok && r == s.tag_phase;
+  }
+  return ok;
 }
 
 }  // namespace vpichip

@@ -412,6 +412,7 @@ int ensure_hydro(Engine *e);
 int k_dump_gather(Engine *e, int what, int layout, const int32_t *words, int nwords, int sx, int sy, int sz, void *out, size_t out_bytes);
 int k_clear_hydro(Engine *e);
 int k_accumulate_hydro_p(Engine *e, Species &s, bool wants_tile);   // moments.hip
+int k_accumulate_hydro_p_select(Engine *e, Species &s, const vpic_hip_select_t &d);   // ... of the particles a checked selection keeps
 int k_hydro_p_untiled(Engine *e, Species &s, bool by_cell);
 HydroConsts hydro_consts(const Engine *e, const Species &s);
 int k_moments_stats(Engine *e, int64_t out[4]);

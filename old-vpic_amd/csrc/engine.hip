@@ -771,6 +771,11 @@ int vpic_hip_clear_jf(vpic_hip_engine_t *e) { ENGINE(e); return k_clear_jf(e); }
 int vpic_hip_clear_jf_unload_accumulator(vpic_hip_engine_t *e) { ENGINE(e); return k_clear_jf_unload_accumulator(e); }
 int vpic_hip_clear_hydro(vpic_hip_engine_t *e) { ENGINE(e); return k_clear_hydro(e); }
 int vpic_hip_accumulate_hydro_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp); return k_accumulate_hydro_p(e, e->species[sp], wants_tile_order(e, e->species[sp])); }
+int vpic_hip_accumulate_hydro_p_select(vpic_hip_engine_t *e, int sp, const vpic_hip_select_t *s) {
+  ENGINE(e); SPECIES(e, sp);
+  if (check_select(s)) return 1;
+  return k_accumulate_hydro_p_select(e, e->species[sp], *s);
+}
 int vpic_hip_moments_stats(vpic_hip_engine_t *e, int64_t out[4]) { ENGINE(e); if (!out) VH_FAIL("Bad output array"); return k_moments_stats(e, out); }
 int vpic_hip_synchronize_hydro(vpic_hip_engine_t *e) { ENGINE(e); return k_synchronize_hydro_local(e); }
 int vpic_hip_local_adjust_hydro(vpic_hip_engine_t *e) { ENGINE(e); return k_local_adjust_hydro(e); }

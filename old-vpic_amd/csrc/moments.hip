@@ -11,8 +11,12 @@
 //               defined here and shared with distribution.hip) -- with global atomics.
 //   finalize    (fixed point) hydro[v].m += (float)(sum / scale_m), one rounding per word and call, and the word is zeroed.
 // The array is not reordered and nothing the push or the next sort relies on is touched.
+// accumulate_hydro_p_select: the same passes over the same array, in instances (SEL) in which a particle that the selection
+// (dist_coords.h: the ranges and the tag conditions of vpic_hip_species_select) does not keep adds nothing; the instances
+// without a selection are the code they were.
 #include "engine.h"
 #include "push_device.h"
+#include "dist_coords.h"
 #include <algorithm>
 #include <math.h>
 
@@ -33,6 +37,12 @@ struct MomK {
   double scale[HYDRO_MOMENTS];                           // fixed point: per moment ([0] alone for rho)
   unsigned long long *stats;                             // live particles, through LDS, through global memory, contributions out of range
 };
+// the selection of an instance: none (today's code), ranges in the box frame, ranges that name a coordinate in the frame of the
+// local field (dist_coords.h: FIELDS); the kernels' argument carries the descriptor only where there is one
+enum { MOM_SEL_NONE = 0, MOM_SEL_BOX = 1, MOM_SEL_FIELD = 2 };
+template <int SEL> struct MomKS : MomK { SelectK sel; const int64_t *tag; };   // tag: null when every tag reads 0
+template <> struct MomKS<MOM_SEL_NONE> : MomK {};
+static_assert(sizeof(MomKS<MOM_SEL_NONE>) == sizeof(MomK), "the instances without a selection take the argument they took");
 
 // tpart[] is a partition of [0, n_sorted): non-decreasing from 0, within n_sorted (*bad is set where it is not)
 __global__ __launch_bounds__(256)
@@ -64,17 +74,37 @@ template <> struct MomLayout<HYDRO_MOMENTS, float> { static constexpr int STRIDE
 struct MomCount { unsigned live = 0, lds = 0, global = 0, range = 0; };
 
 // particle idx: its NM x 8 contributions into the window (lx, ly, lz: its cell within the window, when WINDOW and inside) or
-// into global memory
-template <int NM, typename ACC, bool WINDOW>
-__device__ __forceinline__ void moments_of_particle(const MomK &K, ACC *__restrict__ out, ACC *s_win, long long idx, int bx, int by, int bz, MomCount &n) {
+// into global memory.  SEL: only a particle the selection keeps (the coordinates of dist_coords.h from the STORED momenta and the
+// voxel's interpolator record, which a kept particle reads once: for its coordinates, where they need it, and for its moments)
+// is counted and adds; any other returns before a contribution is formed.
+template <int NM, typename ACC, bool WINDOW, int SEL>
+__device__ __forceinline__ void moments_of_particle(const MomKS<SEL> &K, ACC *__restrict__ out, ACC *s_win, long long idx, int bx, int by, int bz, MomCount &n) {
   const int voxel = K.p.i[idx];
   if (voxel < 0 || voxel >= K.nv_safe) return;            // i < 0: a dead slot (engine.h, Species::n_holes)
-  n.live++;
   HydroP P;
-  if constexpr (NM == HYDRO_MOMENTS)
-    hydro_particle(K.p.dx[idx], K.p.dy[idx], K.p.dz[idx], K.p.ux[idx], K.p.uy[idx], K.p.uz[idx], K.p.q[idx], load_interp(K.fi, voxel), K.h, P);
-  else
-    node_weights(K.p.dx[idx], K.p.dy[idx], K.p.dz[idx], K.p.q[idx], K.h.r8V, P.w);
+  if constexpr (SEL != MOM_SEL_NONE) {
+    static_assert(NM == HYDRO_MOMENTS, "a selection is for the hydro moments");
+    constexpr bool FIELDS = SEL == MOM_SEL_FIELD;
+    if (K.sel.use_tag && !select_tag_ok(K.sel.s, K.tag ? K.tag[idx] : 0)) return;          // (uniform: the tags are read when a flag is set)
+    const DistRaw r{voxel, K.p.dx[idx], K.p.dy[idx], K.p.dz[idx], K.p.ux[idx], K.p.uy[idx], K.p.uz[idx]};
+    InterpK f;
+    if (FIELDS) f = load_interp(K.fi, voxel);
+    if (K.sel.s.n_sel > 0) {
+      const DistField df = FIELDS ? DistField{f.b0, f.b1, f.ex, f.ey, f.ez} : DistField{};
+      int cx = 0, cy = 0, cz = 0;
+      const DistCoords v = dist_coords<FIELDS>(r, df, K.sel.need, K.t, cx, cy, cz);
+      if (!dist_in_ranges<FIELDS>(v, K.sel.s.sel, K.sel.s.n_sel)) return;
+    }
+    if (!FIELDS) f = load_interp(K.fi, voxel);
+    n.live++;
+    hydro_particle(r.dx, r.dy, r.dz, r.ux, r.uy, r.uz, K.p.q[idx], f, K.h, P);
+  } else {
+    n.live++;
+    if constexpr (NM == HYDRO_MOMENTS)
+      hydro_particle(K.p.dx[idx], K.p.dy[idx], K.p.dz[idx], K.p.ux[idx], K.p.uy[idx], K.p.uz[idx], K.p.q[idx], load_interp(K.fi, voxel), K.h, P);
+    else
+      node_weights(K.p.dx[idx], K.p.dy[idx], K.p.dz[idx], K.p.q[idx], K.h.r8V, P.w);
+  }
   bool inside = false;
   int slot0 = 0;
   if (WINDOW) {
@@ -85,6 +115,9 @@ __device__ __forceinline__ void moments_of_particle(const MomK &K, ACC *__restri
     slot0 = (int)(lx + MOM_WX * (ly + MOM_WX * lz));
   }
   unsigned range = 0;
+  // (the selected instances count without a branch: the two increments below, one on either path, become an indexed store
+  // into MomCount in scratch memory in the tile instances, which the instances without a selection keep as they were compiled)
+  if constexpr (SEL != MOM_SEL_NONE) { n.lds += inside ? 1u : 0u; n.global += inside ? 0u : 1u; }
   if (WINDOW && inside) {
 #pragma unroll
     for (int nd = 0; nd < 8; nd++) {
@@ -94,7 +127,7 @@ __device__ __forceinline__ void moments_of_particle(const MomK &K, ACC *__restri
 #pragma unroll
       for (int k = 0; k < NM; k++) mom_add(&s_win[k * MOM_SLOTS + slot], c[k], K.scale[k], range);
     }
-    n.lds++;
+    if constexpr (SEL == MOM_SEL_NONE) n.lds++;
   } else {
     ACC *g = out + (size_t)voxel * MomLayout<NM, ACC>::STRIDE;
 #pragma unroll
@@ -105,7 +138,7 @@ __device__ __forceinline__ void moments_of_particle(const MomK &K, ACC *__restri
 #pragma unroll
       for (int k = 0; k < NM; k++) mom_add(m + k, c[k], K.scale[k], range);
     }
-    n.global++;
+    if constexpr (SEL == MOM_SEL_NONE) n.global++;
   }
   n.range += range;
 }
@@ -120,9 +153,9 @@ __device__ __forceinline__ void publish_counts(const MomCount &n, unsigned long 
   }
 }
 
-template <int NM, typename ACC>
+template <int NM, typename ACC, int SEL = MOM_SEL_NONE>
 __global__ __launch_bounds__(256)
-void moments_tile_kernel(MomK K, ACC *__restrict__ out) {
+void moments_tile_kernel(MomKS<SEL> K, ACC *__restrict__ out) {
   __shared__ ACC s_win[NM * MOM_SLOTS];
   if (*K.bad) return;                                      // (the tail pass takes the whole array)
   const int j = blockIdx.x;
@@ -134,7 +167,7 @@ void moments_tile_kernel(MomK K, ACC *__restrict__ out) {
   const long long begin = K.tpart[(size_t)j * TILE_CELLS];
   const long long end = j + 1 < K.t.ntiles ? (long long)K.tpart[(size_t)(j + 1) * TILE_CELLS] : K.n_sorted;
   MomCount n;
-  for (long long idx = begin + threadIdx.x; idx < end; idx += 256) moments_of_particle<NM, ACC, true>(K, out, s_win, idx, bx, by, bz, n);
+  for (long long idx = begin + threadIdx.x; idx < end; idx += 256) moments_of_particle<NM, ACC, true, SEL>(K, out, s_win, idx, bx, by, bz, n);
   __syncthreads();
   // the non-zero words of the window (only nodes inside the arrays can be: nv_safe)
   for (int w = threadIdx.x; w < NM * MOM_SLOTS; w += 256) {
@@ -149,13 +182,13 @@ void moments_tile_kernel(MomK K, ACC *__restrict__ out) {
   publish_counts(n, K.stats);
 }
 
-template <int NM, typename ACC>
+template <int NM, typename ACC, int SEL = MOM_SEL_NONE>
 __global__ __launch_bounds__(256)
-void moments_tail_kernel(MomK K, ACC *__restrict__ out) {
+void moments_tail_kernel(MomKS<SEL> K, ACC *__restrict__ out) {
   const long long from = K.bad && *K.bad ? 0 : K.n_sorted;
   MomCount n;
   for (long long idx = from + (long long)blockIdx.x * 256 + threadIdx.x; idx < K.np; idx += (long long)gridDim.x * 256)
-    moments_of_particle<NM, ACC, false>(K, out, nullptr, idx, 0, 0, 0, n);
+    moments_of_particle<NM, ACC, false, SEL>(K, out, nullptr, idx, 0, 0, 0, n);
   publish_counts(n, K.stats);
 }
 
@@ -174,8 +207,8 @@ void moments_finalize_kernel(float *__restrict__ out, unsigned long long *__rest
 }
 
 // the kernels of one call: `tiled`: tile pass + tail pass; otherwise the per-particle pass over the whole array
-template <int NM, typename ACC>
-static int launch_moments(Engine *e, Species &s, MomK &K, ACC *out, bool tiled) {
+template <int NM, typename ACC, int SEL = MOM_SEL_NONE>
+static int launch_moments(Engine *e, Species &s, MomKS<SEL> &K, ACC *out, bool tiled) {
   if (e->mom_stats.begin(e->stream)) return 1;
   K.p = s.p; K.fi = reinterpret_cast<const float4 *>(e->fi); K.np = s.np;
   K.sy = e->gk.sy; K.sz = e->gk.sz; K.nv_safe = e->gk.nv - e->gk.sz - e->gk.sy - 1;
@@ -186,11 +219,11 @@ static int launch_moments(Engine *e, Species &s, MomK &K, ACC *out, bool tiled) 
     if (tiled) {
       K.tpart = s.tpart; K.bad = e->mom_stats.bad_partition(); K.n_sorted = s.n_sorted;
       if (k_check_tile_partition(e, s, e->mom_stats.bad_partition())) return 1;
-      hipLaunchKernelGGL((moments_tile_kernel<NM, ACC>), dim3((unsigned)K.t.ntiles), dim3(256), 0, e->stream, K, out);
+      hipLaunchKernelGGL((moments_tile_kernel<NM, ACC, SEL>), dim3((unsigned)K.t.ntiles), dim3(256), 0, e->stream, K, out);
     }
     // (a tpart[] that is no partition sends the whole array through this pass: sized for that)
     const unsigned nb = (unsigned)std::min<long long>(MOM_TAIL_BLOCKS, (s.np + 255) / 256);
-    hipLaunchKernelGGL((moments_tail_kernel<NM, ACC>), dim3(nb), dim3(256), 0, e->stream, K, out);
+    hipLaunchKernelGGL((moments_tail_kernel<NM, ACC, SEL>), dim3(nb), dim3(256), 0, e->stream, K, out);
     VH_CHECK(hipGetLastError());
   }
   e->mom_stats.pending = true;                             // (read when somebody asks: read_moments_stats)
@@ -220,17 +253,12 @@ static MomentPlan plan_for(Engine *e, Species &s, bool wants_tile, bool per_part
   return plan_moments(in);
 }
 
-int k_accumulate_hydro_p(Engine *e, Species &s, bool wants_tile) {
-  if (ensure_hydro(e)) return 1;
-  const MomentPlan pl = plan_for(e, s, wants_tile, e->knobs.hydro_per_particle);
-  if (!e->det_acc && pl.path != MomentPath::tiled) {
-    book_untiled(e, s);
-    return s.np == 0 ? 0 : k_hydro_p_untiled(e, s, pl.path == MomentPath::cells);
-  }
-  if (pl.sort_by_tile_first && k_sort_p(e, s, true)) return 1;
-  MomK K{};
+// the 14 hydro moments of the species through the kernels of this file (`tiled`: launch_moments), in floats or -- deterministic
+// mode -- in fixed point at the scale of the species' q_max, rounded once into the float array; what: the caller, for the message
+template <int SEL>
+static int hydro_sums(Engine *e, Species &s, MomKS<SEL> &K, bool tiled, const char *what) {
   K.h = hydro_consts(e, s);
-  if (!e->det_acc) return launch_moments<HYDRO_MOMENTS, float>(e, s, K, reinterpret_cast<float *>(e->hydro), true);
+  if (!e->det_acc) return launch_moments<HYDRO_MOMENTS, float, SEL>(e, s, K, reinterpret_cast<float *>(e->hydro), tiled);
   const size_t words = (size_t)HYDRO_MOMENTS * (size_t)e->gk.nv;
   if (!e->hydro64) {
     VH_CHECK(hipMalloc((void **)&e->hydro64, sizeof(unsigned long long) * words));
@@ -239,12 +267,12 @@ int k_accumulate_hydro_p(Engine *e, Species &s, bool wants_tile) {
   const MomentScales ms = moment_scales(s.q_max > 0 ? (double)s.q_max : e->acc_qref, s.q_m, K.h.r8V, K.h.c);
   MomInvScales inv;
   for (int k = 0; k < HYDRO_MOMENTS; k++) { K.scale[k] = ms.scale[k]; inv.s[k] = 1.0 / ms.scale[k]; }
-  if (launch_moments<HYDRO_MOMENTS, unsigned long long>(e, s, K, e->hydro64, pl.path == MomentPath::tiled)) return 1;
+  if (launch_moments<HYDRO_MOMENTS, unsigned long long, SEL>(e, s, K, e->hydro64, tiled)) return 1;
   if (read_moments_stats(e)) return 1;                       // (one wait per deterministic call: get_hydro follows)
   if (e->mom_stats.last[3] > 0) {
     VH_CHECK(hipMemsetAsync(e->hydro64, 0, sizeof(unsigned long long) * words, e->stream));
-    VH_FAIL("accumulate_hydro_p: %lld contributions are out of the fixed-point range of the deterministic sums (a momentum |u| of the order of 2^12 and above); nothing was added",
-            (long long)e->mom_stats.last[3]);
+    VH_FAIL("%s: %lld contributions are out of the fixed-point range of the deterministic sums (a momentum |u| of the order of 2^12 and above); nothing was added",
+            what, (long long)e->mom_stats.last[3]);
   }
   hipLaunchKernelGGL(moments_finalize_kernel<HYDRO_MOMENTS>, dim3((unsigned)((e->gk.nv + 255) / 256)), dim3(256), 0, e->stream,
                      reinterpret_cast<float *>(e->hydro), e->hydro64, e->gk.nv, inv);
@@ -252,12 +280,44 @@ int k_accumulate_hydro_p(Engine *e, Species &s, bool wants_tile) {
   return 0;
 }
 
+int k_accumulate_hydro_p(Engine *e, Species &s, bool wants_tile) {
+  if (ensure_hydro(e)) return 1;
+  const MomentPlan pl = plan_for(e, s, wants_tile, e->knobs.hydro_per_particle);
+  if (!e->det_acc && pl.path != MomentPath::tiled) {
+    book_untiled(e, s);
+    return s.np == 0 ? 0 : k_hydro_p_untiled(e, s, pl.path == MomentPath::cells);
+  }
+  if (pl.sort_by_tile_first && k_sort_p(e, s, true)) return 1;
+  MomKS<MOM_SEL_NONE> K{};
+  return hydro_sums(e, s, K, pl.path == MomentPath::tiled, "accumulate_hydro_p");
+}
+
+// ... of the particles a (checked) selection keeps: the species is read and left as it is, in either mode (policy.h:
+// plan_moments_select), and the fixed-point scale is the whole species'
+template <int SEL>
+static int hydro_sums_select(Engine *e, Species &s, const vpic_hip_select_t &d, bool tiled) {
+  MomKS<SEL> K{};
+  K.sel = make_select_k(d);
+  K.tag = s.has_tags ? s.tag : nullptr;                      // never allocated: every tag reads 0
+  return hydro_sums(e, s, K, tiled, "accumulate_hydro_p_select");
+}
+int k_accumulate_hydro_p_select(Engine *e, Species &s, const vpic_hip_select_t &d) {
+  if (ensure_hydro(e)) return 1;
+  MomentInputs in;
+  in.det = e->det_acc; in.tile_valid = s.tile_valid; in.tpart_ok = tile_partition_usable(s, make_tile_k(e->gk));
+  in.tiled_knob = e->knobs.moments_tiled; in.np = s.np; in.nm = s.nm; in.nv = e->gk.nv;
+  const bool tiled = plan_moments_select(in).path == MomentPath::tiled;
+  unsigned need = 0;
+  for (int r = 0; r < d.n_sel; r++) need |= 1u << d.sel[r].coord;
+  return need & NEED_FIELD ? hydro_sums_select<MOM_SEL_FIELD>(e, s, d, tiled) : hydro_sums_select<MOM_SEL_BOX>(e, s, d, tiled);
+}
+
 int k_accumulate_rho_p(Engine *e, Species &s, bool wants_tile) {
   if (s.np == 0 || s.chargeless) { book_untiled(e, s); e->mom_stats.last[0] = e->mom_stats.last[2] = 0; return 0; }   // charge-0 copies add nothing
   const MomentPlan pl = plan_for(e, s, wants_tile, e->knobs.rho_per_particle);
   if (!e->det_acc && pl.path != MomentPath::tiled) { book_untiled(e, s); return k_rho_p_untiled(e, s, pl.path == MomentPath::cells); }
   if (pl.sort_by_tile_first && k_sort_p(e, s, true)) return 1;
-  MomK K{};
+  MomKS<MOM_SEL_NONE> K{};
   K.h.r8V = 0.125 * e->grid.rdx * e->grid.rdy * e->grid.rdz;   // rho_p.c:37
   if (!e->det_acc) return launch_moments<1, float>(e, s, K, e->f.c[F_RHOF], true);
   // deterministic: fixed-point sums in rho64, then one rounding into rhof (the species are added to rhof one after the other,

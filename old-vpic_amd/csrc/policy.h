@@ -398,6 +398,16 @@ inline MomentPlan plan_moments(const MomentInputs &in) {
   return pl;
 }
 
+// accumulate_hydro_p_select: the moments of a selection READ the species and leave it as it is, so no plan of theirs sorts,
+// in either accumulation mode, and the float sums never take the by-cell route (which sorts by voxel).  A species in tile order
+// with a partition on record and no movers in flight is summed by tile (tile pass + tail pass), any other -- also under
+// VPIC_HIP_MOMENTS_TILED=0 -- by the per-particle pass over the whole array.
+inline MomentPlan plan_moments_select(const MomentInputs &in) {
+  MomentPlan pl;
+  pl.path = in.tiled_knob && in.tile_valid && in.tpart_ok && in.nm == 0 ? MomentPath::tiled : MomentPath::per_particle;
+  return pl;
+}
+
 // Fixed-point scales of the 14 hydro moments in deterministic mode (jx jy jz rho px py pz ke txx tyy tzz tyz tzx txy): one
 // power of two each, chosen per call from the species' largest macro-particle charge q_max, its q_m, r8V = 1 / (8 dV) and c.
 // A particle's weight on a node is at most W = 8 r8V q_max, |v| < c, and its time-centred momentum is |u|, so ONE contribution

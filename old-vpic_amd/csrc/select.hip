@@ -20,24 +20,6 @@ constexpr int SEL_PASSES = SEL_CHUNK / (64 * SEL_WAVES);   // passes of a workgr
 constexpr int SEL_MAX_BLOCKS = 4096;                       // workgroups of launches 1 and 3 (each takes every gridDim.x-th chunk)
 static_assert(SEL_CHUNK % 256 == 0 && SEL_GROUPS <= 64, "a chunk is a multiple of 256 particles whose masks one wavefront scans");
 
-struct SelectK {
-  vpic_hip_select_t s;
-  unsigned need;                                           // as DistK::need: the coordinates the ranges name
-  int use_tag;                                             // a tag condition is enabled (the flags of s)
-};
-
-// the tag conditions of a descriptor (all enabled ones must hold)
-__device__ __forceinline__ bool select_tag_ok(const vpic_hip_select_t &s, long long tag) {
-  bool ok = true;
-  if (s.flags & VPIC_HIP_SELECT_TAG_RANGE) ok = ok && tag >= s.tag_lo && tag < s.tag_hi;
-  if (s.flags & VPIC_HIP_SELECT_TAG_EVERY) {
-    long long r = tag % s.tag_every;                       // (|r| < every: r + every cannot overflow)
-    if (r < 0) r += s.tag_every;
-    ok = ok && r == s.tag_phase;
-  }
-  return ok;
-}
-
 // Launch 1.  Chunk c is particles [c * SEL_CHUNK, (c + 1) * SEL_CHUNK) of the array; wavefront w of the workgroup
 // takes the groups of 64 particles w, w + 4, ... of it.  MASKS: the keep masks are stored (mask[] holds SEL_GROUPS
 // words for every chunk, the last chunk's beyond np included: zero).  tag: null when every tag reads 0.
@@ -188,10 +170,7 @@ void select_write_kernel(ParticlesK p, const int64_t *__restrict__ tag, const in
 // first min(kept, cap) records are then in Engine::sel_p / sel_f / sel_i (device).  Waits for the stream; fills
 // Engine::sel_stats.last.  count_only: launch 1 stores no masks.  Reads the species and changes nothing about it.
 int k_species_select(Engine *e, Species &s, const vpic_hip_select_t &d, int64_t cap, bool want_p, bool want_f, bool want_i, bool count_only) {
-  SelectK k{};
-  k.s = d;
-  for (int r = 0; r < d.n_sel; r++) k.need |= 1u << d.sel[r].coord;
-  k.use_tag = (d.flags & (VPIC_HIP_SELECT_TAG_RANGE | VPIC_HIP_SELECT_TAG_EVERY)) != 0;
+  const SelectK k = make_select_k(d);
   const long long np = s.np, n_chunks = (np + SEL_CHUNK - 1) / SEL_CHUNK;
   const int64_t *tag = s.has_tags ? s.tag : nullptr;                         // never allocated: every tag reads 0
   if (grow(e->sel_counts, e->sel_counts_n, (size_t)n_chunks) || grow(e->sel_offsets, e->sel_offsets_n, (size_t)n_chunks)) return 1;

@@ -471,8 +471,16 @@ class Engine:
     def clear_hydro(self):
         self._ck(self._l.vpic_hip_clear_hydro(self._h))
 
-    def accumulate_hydro_p(self, sp):
-        self._ck(self._l.vpic_hip_accumulate_hydro_p(self._h, sp))
+    def accumulate_hydro_p(self, sp, select=(), tag_range=None, tag_every=None):
+        """adds the species' hydro moments to the engine's hydro array; with a selection -- (coord, lo, hi) ranges,
+        tag_range = (lo, hi), tag_every = (every, phase): the arguments of `select`, the same coordinate names -- only the
+        particles that `select` would return add (include/vpic_hip.h: vpic_hip_accumulate_hydro_p_select; the ranges
+        look at the stored momenta and the interpolator as it is loaded, the species is left as it is)."""
+        if not select and tag_range is None and tag_every is None:
+            self._ck(self._l.vpic_hip_accumulate_hydro_p(self._h, sp))
+            return
+        d = select_desc(select, tag_range, tag_every)
+        self._ck(self._l.vpic_hip_accumulate_hydro_p_select(self._h, int(sp), C.byref(d)))
 
     def moments_stats(self):
         """(live particles summed, added through an LDS window, added through global memory, contributions out of the

@@ -620,20 +620,26 @@ void vpic_simulation::distribution(species_t *sp, const vpic_hip_dist_t *d, uint
   }
   CK(vpic_hip_species_distribution(engine, id, &local, counts));
 }
-int64_t vpic_simulation::select_particles(species_t *sp, const vpic_hip_select_t *s, int64_t cap, particle_t *p, float *fields, int64_t *index) {
-  if (!sp) ERROR(("Invalid species"));
-  if (!s) ERROR(("Invalid select arguments"));
-  const int id = resident_id(sp->p);
-  if (!engine || id < 0) ERROR(("select_particles before the run has started is not supported by this host"));
+// a deck's selection for the engine: position ranges from physical units to cells of this domain, as distribution(); every
+// other range -- those in the frame of the local field too -- and the tag conditions as they are
+static vpic_hip_select_t select_in_cells(const vpic_hip_select_t &s, const grid_t *grid) {
   const double origin[3] = {(double)grid->x0, (double)grid->y0, (double)grid->z0};
   const double cell[3] = {(double)grid->dx, (double)grid->dy, (double)grid->dz};
-  vpic_hip_select_t local = *s;                             // position ranges: physical units -> cells of this domain, as distribution()
+  vpic_hip_select_t local = s;
   for (int k = 0; k < 4; k++) {
     vpic_hip_dist_range_t &r = local.sel[k];
     if (r.coord < VPIC_HIP_COORD_X || r.coord > VPIC_HIP_COORD_Z) continue;
     r.lo = (r.lo - origin[r.coord]) / cell[r.coord];
     r.hi = (r.hi - origin[r.coord]) / cell[r.coord];
   }
+  return local;
+}
+int64_t vpic_simulation::select_particles(species_t *sp, const vpic_hip_select_t *s, int64_t cap, particle_t *p, float *fields, int64_t *index) {
+  if (!sp) ERROR(("Invalid species"));
+  if (!s) ERROR(("Invalid select arguments"));
+  const int id = resident_id(sp->p);
+  if (!engine || id < 0) ERROR(("select_particles before the run has started is not supported by this host"));
+  const vpic_hip_select_t local = select_in_cells(*s, grid);
   int64_t count = 0;
   CK(vpic_hip_species_select(engine, id, &local, cap, p, fields, index, &count));
   return count;
@@ -1606,6 +1612,18 @@ void vpic_simulation::hydro_dump(const char *speciesname, DumpParameters &dumpPa
   for (size_t k = 0; k < species_order.size(); k++) if (species_order[k] == sp) id = (int)k;
   CK(vpic_hip_clear_hydro(engine));                       // dump.cxx:1403-1405
   CK(vpic_hip_accumulate_hydro_p(engine, id));
+  x_synchronize_hydro();
+  banded_dump(VPIC_HIP_DUMP_HYDRO, 2 /* dump_type::hydro_dump */, sp->id, sp->q_m, dumpParams);
+}
+void vpic_simulation::hydro_dump(const char *speciesname, DumpParameters &dumpParams, const vpic_hip_select_t *s) {
+  species_t *sp = find_species(speciesname);
+  if (!sp) ERROR(("Invalide species name: %s", speciesname));
+  if (!s) ERROR(("Invalid select arguments"));
+  int id = -1;
+  for (size_t k = 0; k < species_order.size(); k++) if (species_order[k] == sp) id = (int)k;
+  const vpic_hip_select_t local = select_in_cells(*s, grid);
+  CK(vpic_hip_clear_hydro(engine));
+  CK(vpic_hip_accumulate_hydro_p_select(engine, id, &local));   // (on the device, from the resident particles: no mirror is downloaded)
   x_synchronize_hydro();
   banded_dump(VPIC_HIP_DUMP_HYDRO, 2 /* dump_type::hydro_dump */, sp->id, sp->q_m, dumpParams);
 }

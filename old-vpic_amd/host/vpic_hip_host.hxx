@@ -279,6 +279,13 @@ public:
   void dump_restart(const char *fbase, int fname_tag = 1);
   void field_dump(DumpParameters &dumpParams);
   void hydro_dump(const char *speciesname, DumpParameters &dumpParams);
+  // ... of the particles a selection keeps (vpic_hip_accumulate_hydro_p_select, include/vpic_hip.h): the same file -- header,
+  // strides, band or interleave -- holding the moments of the kept particles only.  Position ranges are in PHYSICAL units,
+  // converted as select_particles() converts them; ranges in the frame of the local field pass through untouched and, like
+  // every range, look at the stored momenta and at the interpolator on the device as it stands at that point of the step.
+  // Every rank sums its own particles and synchronize_hydro joins the faces as for the whole species.  The particle
+  // mirror does not become resident.
+  void hydro_dump(const char *speciesname, DumpParameters &dumpParams, const vpic_hip_select_t *s);
   size_t px, py, pz;            // domain topology (vpic.hxx:171)
   inline double courant_length(double lx, double ly, double lz, double nx, double ny, double nz) {
     double w0, w1 = 0;
