@@ -391,6 +391,51 @@ int vpic_hip_species_distribution(vpic_hip_engine_t *e, int sp, const vpic_hip_d
  * Misses cost time, never the result. */
 int vpic_hip_species_distribution_stats(vpic_hip_engine_t *e, int64_t out[4]);
 
+/* ---- per-bin sums of particle quantities: beside the count of every bin of a histogram, up to four sums over the
+ * particles counted in it, as exact integers (csrc/distribution.hip) ----
+ * The descriptor d is vpic_hip_species_distribution's: axes, ranges, live and dead slots and the counted test are
+ * exactly those, and counts[] (which may be NULL) equals, bit for bit, what that call returns for the same d.
+ * A value is the product of three factors.  A factor is a VPIC_HIP_COORD_* code other than LOG10_KE -- the coordinate
+ * as stated above; LOG10_KE stays an axis and a range only, the device's and the host's log10 may differ in the last
+ * bit -- or one of the four codes below.  Everything is IEEE double, every operation rounded once, unfused:
+ *   ONE        1.0 (fills the factors a value does not use: x * 1.0 is x)
+ *   Q          (double)q, the stored float macro-charge of the particle -- its weight.  The q array is read only when
+ *              a value names it (4 B per particle).
+ *     gamma  = sqrt(((1 + ux*ux) + uy*uy) + uz*uz)      (KE's expression before the - 1; ux, uy, uz promoted)
+ *   EDOTV      ((Ex*ux + Ey*uy) + Ez*uz) / gamma         Ex, Ey, Ez the float fields at the particle as
+ *              vpic_hip_species_select forms them, promoted to double: E . v in units of c
+ *   EPAR_VPAR  (E_PAR * U_PAR) / gamma                   with E_PAR and U_PAR as stated above: the share of E . v
+ *              that the field along B does
+ *   EDOTV and EPAR_VPAR read all 72 bytes of the voxel's interpolator record, as E_PAR does, and run in the kernel
+ *   instances of the field coordinates; so does every value that names one of those.
+ * Value k of a COUNTED particle:  val = (f0 * f1) * f2,  t = val / quantum.  When fabs(t) < 4294967296.0 (2^32) the
+ * particle adds llrint(t) -- round to nearest, ties to even -- to its bin of sums[k]; otherwise (a NaN included) it adds
+ * nothing to value k and is counted as refused for it: it is still counted in counts[], and the other values still
+ * take it.  A species holds fewer than 2^31 particles and every addend is below 2^32 in magnitude, so no int64 sum can
+ * wrap.  quantum is the resolution the caller asks for: at the coarsest 2^-32 of the largest |val| it expects (a coarser
+ * one cannot be had: larger values are refused), finer where the values allow.  sum of val over a bin = sums * quantum
+ * to within half a quantum per particle.  The sums are integers: they are the same bit for bit whatever order the
+ * array is in and on either path below, and the sums of several ranks add exactly. */
+enum { VPIC_HIP_FACTOR_ONE = 32, VPIC_HIP_FACTOR_Q, VPIC_HIP_FACTOR_EDOTV, VPIC_HIP_FACTOR_EPAR_VPAR };   /* 32..35 */
+typedef struct { int32_t factor[3]; int32_t pad; double quantum; } vpic_hip_dist_value_t;   /* val = (f0 * f1) * f2, in units of quantum */
+VPIC_HIP_STATIC_ASSERT(sizeof(vpic_hip_dist_value_t) == 24, "vpic_hip_dist_value_t layout");
+#define VPIC_HIP_DIST_MAX_VALUES 4
+/* counts: n0 * n1 uint64 in host memory, or NULL; sums: n_val * n0 * n1 int64 in host memory, sums[k * n0*n1 + b1*n0 + b0].
+ * Fails (non-zero, vpic_hip_last_error) on everything vpic_hip_species_distribution fails on (but for the NULL counts),
+ * n_val outside 1..VPIC_HIP_DIST_MAX_VALUES, a NULL v or sums, an unknown factor or LOG10_KE as a factor, or a quantum
+ * that is not positive and finite.  Returns 0 when particles were refused: the caller reads the statistics.  The species,
+ * its order, its bookkeeping and the host mirrors are left exactly as they were. */
+int vpic_hip_species_distribution_sums(vpic_hip_engine_t *e, int sp, const vpic_hip_dist_t *d,
+                                       const vpic_hip_dist_value_t *v, int n_val, uint64_t *counts, int64_t *sums);
+/* The last call: out[0..3] as vpic_hip_species_distribution_stats (live particles seen, kept, counted, counted through
+ * global memory), out[4 + k] the particles refused for value k (0 for k >= n_val).  Two paths (distribution.hip):
+ *   n0 * n1 * (1 + 2 n_val) <= VPIC_HIP_DIST_LDS_BINS -- the 32-bit counts and n_val rows of 64-bit sums fit the 32 KB
+ *     of the histogram's LDS path: every workgroup keeps all of them in LDS (64-bit LDS integer atomics for the sums) and
+ *     adds them to global memory once, at the end; out[3] is 0.  That is 2730, 1638, 1170, 910 bins for 1 to 4 values.
+ *   Larger: every counted particle adds in global memory, the lanes of a wavefront that share a bin combining first,
+ *     and out[3] == out[2].  (There is no sliding window for sums: a position axis makes no difference.) */
+int vpic_hip_species_distribution_sums_stats(vpic_hip_engine_t *e, int64_t out[8]);
+
 /* ---- selected particles of a species: those inside up to four ranges and with the tags asked for, gathered into dense
  * arrays where the particles are, so that only they come to the host (csrc/select.hip) ----
  * Live particles: 0 <= i < nv; dead slots (i = -1) are skipped, particles appended since the last sort are included.

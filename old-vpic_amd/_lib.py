@@ -100,6 +100,8 @@ def lib():
     L.vpic_hip_energy_spectrum_stats.argtypes = [C.c_void_p, C.c_void_p]
     L.vpic_hip_species_distribution.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.vpic_hip_species_distribution_stats.argtypes = [C.c_void_p, C.c_void_p]
+    L.vpic_hip_species_distribution_sums.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.vpic_hip_species_distribution_sums_stats.argtypes = [C.c_void_p, C.c_void_p]
     L.vpic_hip_moments_stats.argtypes = [C.c_void_p, C.c_void_p]
     L.vpic_hip_species_select_count.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.vpic_hip_species_select.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 4
@@ -124,5 +126,6 @@ vpic_hip_synchronize_jf_self vpic_hip_face_count vpic_hip_pack_tang_b vpic_hip_u
 vpic_hip_pack_jf vpic_hip_unpack_jf vpic_hip_step vpic_hip_profile_enable vpic_hip_profile_read vpic_hip_profile_read_sorting vpic_hip_sort_advance_p vpic_hip_species_get_tile_partition vpic_hip_profile_read_species vpic_hip_comm_unique_id vpic_hip_comm_create vpic_hip_comm_destroy vpic_hip_comm_start vpic_hip_comm_finish vpic_hip_comm_stats vpic_hip_comm_timing vpic_hip_species_stats
 vpic_hip_energy_spectrum vpic_hip_energy_bands vpic_hip_energy_spectrum_stats
 vpic_hip_species_distribution vpic_hip_species_distribution_stats vpic_hip_moments_stats
+vpic_hip_species_distribution_sums vpic_hip_species_distribution_sums_stats
 vpic_hip_species_select_count vpic_hip_species_select vpic_hip_species_select_stats
 vpic_hip_accumulate_hydro_p_select""".split()

@@ -136,6 +136,54 @@ __device__ __forceinline__ DistCoords dist_coords(const DistRaw &r, const DistFi
   return v;
 }
 
+// ---- the factors of a per-bin sum beyond the coordinates (vpic_hip_species_distribution_sums: VPIC_HIP_FACTOR_*) ----
+// bits of a `vneed` mask: which of them a value names.  What they share with the coordinates they ask for through `need`
+// (dist_factor_need): the momenta through KE's bit, the whole record and E_PAR, U_PAR through those coordinates' bits, so
+// that dist_load, dist_gather and dist_coords serve them as they are; EDOTV and EPAR_VPAR therefore run in FIELDS instances.
+constexpr unsigned VAL_Q = 1u, VAL_EDOTV = 2u, VAL_EPAR_VPAR = 4u;
+// (host) the `need` and `vneed` bits of one factor code of a checked value
+inline void dist_factor_need(int code, unsigned &need, unsigned &vneed) {
+  if (code < VPIC_HIP_FACTOR_ONE) { need |= 1u << code; return; }
+  if (code == VPIC_HIP_FACTOR_Q) vneed |= VAL_Q;
+  if (code == VPIC_HIP_FACTOR_EDOTV) { vneed |= VAL_EDOTV; need |= 1u << VPIC_HIP_COORD_KE | NEED_FIELD_E; }
+  if (code == VPIC_HIP_FACTOR_EPAR_VPAR) { vneed |= VAL_EPAR_VPAR; need |= 1u << VPIC_HIP_COORD_KE | NEED_FIELD_E | 1u << VPIC_HIP_COORD_U_PAR; }
+}
+
+struct DistExtra { double q, edotv, epar_vpar; };
+
+// the q of one pass, read only when a value names it
+__device__ __forceinline__ float dist_load_q(const ParticlesK &p, long long idx, long long end, unsigned vneed) {
+  return (vneed & VAL_Q) && idx < end ? p.q[idx] : 0.f;
+}
+
+// Of a LIVE particle whose coordinates v dist_coords has formed under dist_factor_need's bits.  E at the particle is
+// formed again by the expressions of dist_coords (the same float operations give the same floats).
+template <bool FIELDS>
+__device__ __forceinline__ DistExtra dist_extra(const DistRaw &r, const DistField &f, float q, const DistCoords &v, unsigned vneed) {
+  DistExtra x{};
+  x.q = (double)q;
+  if (FIELDS && (vneed & (VAL_EDOTV | VAL_EPAR_VPAR))) {
+    const double gamma = sqrt(((1.0 + v.ux * v.ux) + v.uy * v.uy) + v.uz * v.uz);   // KE's expression before the - 1
+    if (vneed & VAL_EDOTV) {
+      const float ex = (f.ex.x + r.dy * f.ex.y) + r.dz * (f.ex.z + r.dy * f.ex.w);
+      const float ey = (f.ey.x + r.dz * f.ey.y) + r.dx * (f.ey.z + r.dz * f.ey.w);
+      const float ez = (f.ez.x + r.dx * f.ez.y) + r.dy * (f.ez.z + r.dx * f.ez.w);
+      x.edotv = (((double)ex * v.ux + (double)ey * v.uy) + (double)ez * v.uz) / gamma;
+    }
+    if (vneed & VAL_EPAR_VPAR) x.epar_vpar = (v.e_par * v.u_par) / gamma;
+  }
+  return x;
+}
+
+// a select chain over the factor codes, as dist_coord over the coordinates (the code is uniform)
+template <bool FIELDS>
+__device__ __forceinline__ double dist_factor(const DistCoords &v, const DistExtra &x, int code) {
+  if (code >= VPIC_HIP_FACTOR_ONE)
+    return code == VPIC_HIP_FACTOR_ONE ? 1.0 : code == VPIC_HIP_FACTOR_Q ? x.q
+         : FIELDS && code == VPIC_HIP_FACTOR_EDOTV ? x.edotv : x.epar_vpar;
+  return dist_coord<FIELDS>(v, code);
+}
+
 // ---- a whole selection (vpic_hip_select_t): the ranges and the tag conditions, for select.hip and the selected moments of
 // moments.hip ----
 struct SelectK {

@@ -5,6 +5,8 @@
 // Which path a descriptor takes, the window's shape and how tiles are dealt to wavefronts are host decisions in policy.h
 // (plan_distribution, plan_dist_tiles, plan_chunks); the window protocol, add_together, the check of the tile partition
 // and the statistics block are the ones every pass over a species uses (engine.h).
+// Behind the histograms: the per-bin sums of particle quantities (vpic_hip_species_distribution_sums), kernel instances of their
+// own over the same loads, coordinates and counted test; 64-bit integer sums, in LDS while they fit (policy.h, plan_distribution_sums).
 #include "dist_coords.h"
 #include <algorithm>
 
@@ -259,6 +261,183 @@ int k_species_distribution(Engine *e, Species &s, const vpic_hip_dist_t &d) {
   }
   VH_CHECK(hipMemcpyAsync(e->dist_host, e->dist_counts, bins * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
   return e->dist_stats.read(e->stream);
+}
+
+// ---- per-bin sums of particle quantities (vpic_hip_species_distribution_sums; include/vpic_hip.h states the arithmetic) ----
+struct DistSumsK {
+  vpic_hip_dist_t d;
+  vpic_hip_dist_value_t v[VPIC_HIP_DIST_MAX_VALUES];
+  unsigned need, vneed;                        // need: as DistK::need, the factors' coordinates included; vneed: VAL_* (dist_coords.h)
+  int n0, n1, n_val;
+};
+
+// From this many lanes in the first counted lane's bin on they add their addends up across the wavefront and that lane
+// adds once (a cold beam puts a whole wavefront in one word, and adds to one word are served one after the other); fewer
+// add for themselves, which costs less than the six exchanges of a 64-bit word the adding-up takes per value.
+constexpr int SUMS_TOGETHER_MIN = 8;
+
+// the lanes for which `on` holds add `x` to word[a]; together: those of `same` (the lanes that share lane lead's word)
+// add once
+__device__ __forceinline__ void add_sums_together(unsigned long long *word, int a, long long x, bool on, bool together,
+                                                  unsigned long long same, int lead, int lane) {
+  bool mine = on;
+  if (together) {
+    const bool shared = same >> lane & 1ull;
+    long long s = shared ? x : 0;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+    if (shared) { mine = lane == lead; x = s; }
+  }
+  if (mine && x) atomicAdd(word + a, (unsigned long long)x);                 // (two's complement: the unsigned add is the signed one)
+}
+
+// One pass over the species, every wavefront a contiguous chunk, as species_distribution_kernel walks it (the same loads
+// ahead, the same coordinates, the same counted test), plus q when a value names it.
+//   DIST_LDS: the workgroup's LDS holds n_val rows of 64-bit sums, then the 32-bit counts; added to global memory at the end.
+//   DIST_GLOBAL: every counted particle adds to counts[] and sums[] and is counted as a miss.
+// Integer adds: any order and any grouping of them gives the same words.
+// stats: live particles seen, kept by the selection, counted, misses, then the particles refused for each value.
+template <int PATH, bool FIELDS>
+__global__ __launch_bounds__(64 * DIST_WAVES)
+void species_distribution_sums_kernel(ParticlesK p, long long np, long long chunk, DistSumsK k, GridK g, TileK t,
+                                      unsigned long long *__restrict__ counts, unsigned long long *__restrict__ sums,
+                                      unsigned long long *__restrict__ stats, const vpic_interpolator_t *__restrict__ fi) {
+  extern __shared__ unsigned long long s_sums[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int bins = k.n0 * k.n1;
+  unsigned *s_counts = reinterpret_cast<unsigned *>(s_sums + k.n_val * bins);
+  if (PATH == DIST_LDS) {
+    for (int j = threadIdx.x; j < k.n_val * bins; j += 64 * DIST_WAVES) s_sums[j] = 0;
+    for (int j = threadIdx.x; j < bins; j += 64 * DIST_WAVES) s_counts[j] = 0;
+    __syncthreads();
+  }
+  const long long w = (long long)blockIdx.x * DIST_WAVES + wave;
+  const long long begin = w * chunk, end = begin + chunk < np ? begin + chunk : np;
+  unsigned long long n_seen = 0, n_kept = 0, n_counted = 0, n_refused[VPIC_HIP_DIST_MAX_VALUES] = {0, 0, 0, 0};
+  DistRaw next = dist_load<FIELDS>(p, begin + lane, end, k.need), next2{};
+  float q_next = dist_load_q(p, begin + lane, end, k.vneed), q_next2 = 0.f;
+  DistField f{}, f_next{};
+  if (FIELDS) {
+    next2 = dist_load<FIELDS>(p, begin + 64 + lane, end, k.need);
+    q_next2 = dist_load_q(p, begin + 64 + lane, end, k.vneed);
+    f_next = dist_gather(fi, next.voxel, g.nv, k.need);
+  }
+  for (long long at = begin; at < end; at += 64) {
+    const DistRaw r = next;
+    const float q = q_next;
+    if (FIELDS) {
+      f = f_next;
+      next = next2; q_next = q_next2;
+      f_next = dist_gather(fi, next.voxel, g.nv, k.need);
+      next2 = dist_load<FIELDS>(p, at + 128 + lane, end, k.need);
+      q_next2 = dist_load_q(p, at + 128 + lane, end, k.vneed);
+    } else {
+      next = dist_load<FIELDS>(p, at + 64 + lane, end, k.need);
+      q_next = dist_load_q(p, at + 64 + lane, end, k.vneed);
+    }
+    const bool live = r.voxel >= 0 && r.voxel < g.nv;
+    n_seen += __popcll(__ballot(live));
+    if (!__any(live)) continue;
+    DistCoords v{};
+    if (live) {
+      int cx = 0, cy = 0, cz = 0;
+      v = dist_coords<FIELDS>(r, f, k.need, t, cx, cy, cz);
+    }
+    const bool kept = live && dist_in_ranges<FIELDS>(v, k.d.sel, k.d.n_sel);
+    n_kept += __popcll(__ballot(kept));
+    bool counted = kept;
+    int b0 = 0, b1 = 0;
+    {
+      const double t0 = (dist_coord<FIELDS>(v, k.d.axis[0].coord) - k.d.axis[0].lo) / k.d.axis[0].d;
+      counted = counted && t0 >= 0.0 && t0 < (double)k.n0;
+      b0 = counted ? (int)t0 : 0;
+    }
+    if (k.d.n_axes == 2) {
+      const double t1 = (dist_coord<FIELDS>(v, k.d.axis[1].coord) - k.d.axis[1].lo) / k.d.axis[1].d;
+      counted = counted && t1 >= 0.0 && t1 < (double)k.n1;
+      b1 = counted ? (int)t1 : 0;
+    }
+    const unsigned long long counted_mask = __ballot(counted);
+    n_counted += __popcll(counted_mask);
+    if (!counted_mask) continue;
+    const int a = b1 * k.n0 + b0;                                            // (below bins; 0 for a lane that is not counted)
+    if (PATH == DIST_LDS) add_together(s_counts, a, counted, lane);
+    else add_together(counts, a, counted, lane);
+
+    const DistExtra x = dist_extra<FIELDS>(r, f, q, v, k.vneed);
+    const int lead = __ffsll((long long)counted_mask) - 1;
+    const int a0 = __builtin_amdgcn_readlane(a, lead);
+    const unsigned long long same = __ballot(counted && a == a0);
+    const bool together = __popcll(same) >= SUMS_TOGETHER_MIN;
+#pragma unroll
+    for (int j = 0; j < VPIC_HIP_DIST_MAX_VALUES; j++) {
+      if (j >= k.n_val) break;
+      const vpic_hip_dist_value_t &val = k.v[j];
+      const double product = (dist_factor<FIELDS>(v, x, val.factor[0]) * dist_factor<FIELDS>(v, x, val.factor[1])) * dist_factor<FIELDS>(v, x, val.factor[2]);
+      const double tq = product / val.quantum;
+      const bool taken = counted && fabs(tq) < 4294967296.0;                 // (a NaN is refused)
+      n_refused[j] += __popcll(__ballot(counted && !taken));
+      const long long addend = taken ? llrint(tq) : 0;
+      if (PATH == DIST_LDS) add_sums_together(s_sums + j * bins, a, addend, taken, together, same, lead, lane);
+      else add_sums_together(sums + (size_t)j * bins, a, addend, taken, together, same, lead, lane);
+    }
+  }
+  if (lane == 0 && n_seen) {
+    atomicAdd(&stats[0], n_seen);
+    if (n_kept) atomicAdd(&stats[1], n_kept);
+    if (n_counted) atomicAdd(&stats[2], n_counted);
+    if (PATH == DIST_GLOBAL && n_counted) atomicAdd(&stats[3], n_counted);
+#pragma unroll
+    for (int j = 0; j < VPIC_HIP_DIST_MAX_VALUES; j++)
+      if (n_refused[j]) atomicAdd(&stats[4 + j], n_refused[j]);
+  }
+  if (PATH == DIST_LDS) {
+    __syncthreads();
+    for (int j = threadIdx.x; j < bins; j += 64 * DIST_WAVES)
+      if (s_counts[j]) atomicAdd(&counts[j], (unsigned long long)s_counts[j]);
+    for (int j = threadIdx.x; j < k.n_val * bins; j += 64 * DIST_WAVES)
+      if (s_sums[j]) atomicAdd(&sums[j], s_sums[j]);
+  }
+}
+
+// the histogram and the sums of species s into Engine::dist_counts / dist_host and dist_sums / dist_sums_host, the eight statistics
+// into dist_sums_last, after the stream has been waited for
+int k_species_distribution_sums(Engine *e, Species &s, const vpic_hip_dist_t &d, const vpic_hip_dist_value_t *v, int n_val) {
+  DistSumsK k{};
+  k.d = d;
+  k.n0 = d.axis[0].n; k.n1 = d.n_axes == 2 ? d.axis[1].n : 1;
+  k.n_val = n_val;
+  for (int a = 0; a < d.n_axes; a++) k.need |= 1u << d.axis[a].coord;
+  for (int r = 0; r < d.n_sel; r++) k.need |= 1u << d.sel[r].coord;
+  for (int j = 0; j < n_val; j++) {
+    k.v[j] = v[j];
+    for (int c = 0; c < 3; c++) dist_factor_need(v[j].factor[c], k.need, k.vneed);
+  }
+  const size_t bins = (size_t)k.n0 * (size_t)k.n1, words = bins * (size_t)n_val;
+  const DistSumsPlan pl = plan_distribution_sums((long long)bins, n_val, VPIC_HIP_DIST_LDS_BINS);
+  if (grow(e->dist_counts, e->dist_bins, bins) || grow_pinned(e->dist_host, e->dist_host_bins, bins) ||
+      grow(e->dist_sums, e->dist_sums_words, words) || grow_pinned(e->dist_sums_host, e->dist_sums_host_words, words)) return 1;
+  if (!e->dist_sums_stats) VH_CHECK(hipMalloc((void **)&e->dist_sums_stats, DIST_SUMS_STATS * sizeof(unsigned long long)));
+  if (!e->dist_sums_stats_host) VH_CHECK(hipHostMalloc((void **)&e->dist_sums_stats_host, DIST_SUMS_STATS * sizeof(unsigned long long), hipHostMallocDefault));
+  VH_CHECK(hipMemsetAsync(e->dist_sums_stats, 0, DIST_SUMS_STATS * sizeof(unsigned long long), e->stream));
+  VH_CHECK(hipMemsetAsync(e->dist_counts, 0, bins * sizeof(unsigned long long), e->stream));
+  VH_CHECK(hipMemsetAsync(e->dist_sums, 0, words * sizeof(unsigned long long), e->stream));
+  if (s.np > 0) {
+    const Chunks ch = plan_chunks(s.np, DIST_WAVES);
+    const size_t lds = sizeof(unsigned) * (size_t)pl.words;
+    const bool fields = (k.need & NEED_FIELD) != 0;
+    auto kernel = fields ? (pl.path == DIST_LDS ? species_distribution_sums_kernel<DIST_LDS, true> : species_distribution_sums_kernel<DIST_GLOBAL, true>)
+                         : (pl.path == DIST_LDS ? species_distribution_sums_kernel<DIST_LDS, false> : species_distribution_sums_kernel<DIST_GLOBAL, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)ch.groups), dim3(64 * DIST_WAVES), lds, e->stream, s.p, (long long)s.np, ch.chunk, k, e->gk,
+                       make_tile_k(e->gk), e->dist_counts, e->dist_sums, e->dist_sums_stats, (const vpic_interpolator_t *)e->fi);
+    VH_CHECK(hipGetLastError());
+  }
+  VH_CHECK(hipMemcpyAsync(e->dist_host, e->dist_counts, bins * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+  VH_CHECK(hipMemcpyAsync(e->dist_sums_host, e->dist_sums, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+  VH_CHECK(hipMemcpyAsync(e->dist_sums_stats_host, e->dist_sums_stats, DIST_SUMS_STATS * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+  VH_CHECK(hipStreamSynchronize(e->stream));
+  for (int j = 0; j < DIST_SUMS_STATS; j++) e->dist_sums_last[j] = (int64_t)e->dist_sums_stats_host[j];
+  return 0;
 }
 
 }  // namespace vpichip

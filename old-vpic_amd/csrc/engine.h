@@ -335,6 +335,11 @@ struct Engine {
   // pinned buffer they come back through; statistics {seen, kept, counted, misses}
   unsigned long long *dist_counts = nullptr, *dist_host = nullptr; size_t dist_bins = 0, dist_host_bins = 0;
   DiagStats dist_stats;
+  // ... and the per-bin sums beside them (vpic_hip_species_distribution_sums), allocated by the first call and grown on
+  // demand: n_val rows of 64-bit sums and the pinned buffer they come back through; statistics {seen, kept, counted,
+  // through global memory, refused for value 0 .. 3} on the device, pinned, and as read by the last call
+  unsigned long long *dist_sums = nullptr, *dist_sums_host = nullptr; size_t dist_sums_words = 0, dist_sums_host_words = 0;
+  unsigned long long *dist_sums_stats = nullptr, *dist_sums_stats_host = nullptr; int64_t dist_sums_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // hydro moments and rho summed by tile (moments.hip), allocated by the first call: the fixed-point words of the
   // deterministic hydro sums (14 per voxel, zero between calls); statistics {live, through LDS, through global memory, out
   // of range} (mom_stats.pending: the last call's are still on the device, not read yet)
@@ -439,6 +444,8 @@ int k_center_p(Engine *e, Species &s, bool uncenter);
 int k_energy_spectrum(Engine *e, Species &s, const vpic_hip_spectrum_t &sp);   // into Engine::spec_lin / spec_log / spec_log_host; waits for the stream
 int k_energy_bands(Engine *e, int n_lin);                                        // Engine::spec_lin -> spec_bands
 int k_species_distribution(Engine *e, Species &s, const vpic_hip_dist_t &d);     // into Engine::dist_counts / dist_host; waits for the stream
+constexpr int DIST_SUMS_STATS = 8;       // words of Engine::dist_sums_stats
+int k_species_distribution_sums(Engine *e, Species &s, const vpic_hip_dist_t &d, const vpic_hip_dist_value_t *v, int n_val);   // ... and into dist_sums / dist_sums_host
 // select.hip: launches 1 and 2 (count_only: no masks), and launch 3 into Engine::sel_p / sel_f / sel_i where asked for; waits for the stream
 int k_species_select(Engine *e, Species &s, const vpic_hip_select_t &d, int64_t cap, bool want_p, bool want_f, bool want_i, bool count_only);
 int k_sort_p(Engine *e, Species &s, bool tile_order = false, bool may_fuse = false);   // may_fuse: the caller pushes the species next (see Species::fuse_pending)

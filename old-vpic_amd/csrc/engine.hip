@@ -192,6 +192,7 @@ static void destroy(Engine *e) {
   (void)hipFree(e->acc64); (void)hipFree(e->rho64);
   (void)hipFree(e->spec_lin); (void)hipFree(e->spec_bands); (void)hipFree(e->spec_log); (void)hipHostFree(e->spec_log_host);
   (void)hipFree(e->dist_counts); (void)hipHostFree(e->dist_host); (void)hipFree(e->hydro64);
+  (void)hipFree(e->dist_sums); (void)hipHostFree(e->dist_sums_host); (void)hipFree(e->dist_sums_stats); (void)hipHostFree(e->dist_sums_stats_host);
   (void)hipFree(e->sel_mask); (void)hipFree(e->sel_offsets); (void)hipFree(e->sel_counts);
   (void)hipFree(e->sel_p); (void)hipFree(e->sel_f); (void)hipFree(e->sel_i);
   for (DiagStats *st : {&e->spec_stats, &e->dist_stats, &e->mom_stats, &e->sel_stats}) { (void)hipFree(st->dev); (void)hipHostFree(st->host); }
@@ -709,13 +710,12 @@ static int copy_stats(const DiagStats &st, int64_t *out, int n) {
   return 0;
 }
 int vpic_hip_energy_spectrum_stats(vpic_hip_engine_t *e, int64_t out[2]) { ENGINE(e); return copy_stats(e->spec_stats, out, 2); }
-int vpic_hip_species_distribution(vpic_hip_engine_t *e, int sp, const vpic_hip_dist_t *d, uint64_t *counts) {
-  ENGINE(e); SPECIES(e, sp);
+// a distribution's descriptor; bins: n0 * n1
+static int check_distribution(const vpic_hip_dist_t *d, long long &bins) {
   if (!d) VH_FAIL("Bad distribution descriptor");
-  if (!counts) VH_FAIL("Bad counts array");
   if (d->n_axes != 1 && d->n_axes != 2) VH_FAIL("distribution: %d axes (1 or 2)", d->n_axes);
   if (check_range_count("distribution", d->n_sel)) return 1;   // (the order of the checks: count, axes, the ranges' coordinates)
-  long long bins = 1;
+  bins = 1;
   for (int a = 0; a < d->n_axes; a++) {
     const vpic_hip_dist_axis_t &x = d->axis[a];
     if (!known_coord(x.coord)) VH_FAIL("distribution: unknown coordinate %d of axis %d", x.coord, a);
@@ -725,6 +725,13 @@ int vpic_hip_species_distribution(vpic_hip_engine_t *e, int sp, const vpic_hip_d
   }
   if (check_ranges("distribution", d->sel, d->n_sel)) return 1;
   if (bins > VPIC_HIP_DIST_MAX_BINS) VH_FAIL("distribution: %lld bins above the cap of %d", bins, VPIC_HIP_DIST_MAX_BINS);
+  return 0;
+}
+int vpic_hip_species_distribution(vpic_hip_engine_t *e, int sp, const vpic_hip_dist_t *d, uint64_t *counts) {
+  ENGINE(e); SPECIES(e, sp);
+  if (d && !counts) VH_FAIL("Bad counts array");
+  long long bins = 0;
+  if (check_distribution(d, bins)) return 1;
   const size_t bytes = sizeof(uint64_t) * (size_t)bins;
   host_will_write(counts, bytes);
   if (k_species_distribution(e, e->species[sp], *d)) return 1;
@@ -732,6 +739,36 @@ int vpic_hip_species_distribution(vpic_hip_engine_t *e, int sp, const vpic_hip_d
   return 0;
 }
 int vpic_hip_species_distribution_stats(vpic_hip_engine_t *e, int64_t out[4]) { ENGINE(e); return copy_stats(e->dist_stats, out, 4); }
+int vpic_hip_species_distribution_sums(vpic_hip_engine_t *e, int sp, const vpic_hip_dist_t *d, const vpic_hip_dist_value_t *v, int n_val,
+                                       uint64_t *counts, int64_t *sums) {
+  ENGINE(e); SPECIES(e, sp);
+  long long bins = 0;
+  if (check_distribution(d, bins)) return 1;
+  if (n_val < 1 || n_val > VPIC_HIP_DIST_MAX_VALUES) VH_FAIL("distribution sums: %d values (1 to %d)", n_val, VPIC_HIP_DIST_MAX_VALUES);
+  if (!v) VH_FAIL("Bad values array");
+  if (!sums) VH_FAIL("Bad sums array");
+  for (int k = 0; k < n_val; k++) {
+    for (int c = 0; c < 3; c++) {
+      const int f = v[k].factor[c];
+      const bool known = (known_coord(f) && f != VPIC_HIP_COORD_LOG10_KE) || (f >= VPIC_HIP_FACTOR_ONE && f <= VPIC_HIP_FACTOR_EPAR_VPAR);
+      if (!known) VH_FAIL("distribution sums: factor %d of value %d is %d, not a factor", c, k, f);
+    }
+    if (!(v[k].quantum > 0) || !std::isfinite(v[k].quantum)) VH_FAIL("distribution sums: quantum %g of value %d", v[k].quantum, k);
+  }
+  const size_t count_bytes = sizeof(uint64_t) * (size_t)bins, sum_bytes = count_bytes * (size_t)n_val;
+  if (counts) host_will_write(counts, count_bytes);
+  host_will_write(sums, sum_bytes);
+  if (k_species_distribution_sums(e, e->species[sp], *d, v, n_val)) return 1;
+  if (counts) memcpy(counts, e->dist_host, count_bytes);
+  memcpy(sums, e->dist_sums_host, sum_bytes);
+  return 0;
+}
+int vpic_hip_species_distribution_sums_stats(vpic_hip_engine_t *e, int64_t out[8]) {
+  ENGINE(e);
+  if (!out) VH_FAIL("Bad output");
+  for (int j = 0; j < DIST_SUMS_STATS; j++) out[j] = e->dist_sums_last[j];
+  return 0;
+}
 static int check_select(const vpic_hip_select_t *s) {
   if (!s) VH_FAIL("Bad select descriptor");
   if (check_ranges("select", s->sel, s->n_sel)) return 1;

@@ -330,6 +330,20 @@ inline DistPlan plan_distribution(int n_axes, const int n[2], const double d[2],
   return pl;
 }
 
+// distribution.hip, the per-bin sums (vpic_hip_species_distribution_sums): which of the two paths bins x n_val values take,
+// and the LDS words of it.  A bin holds one 32-bit count and n_val 64-bit sums, 1 + 2 n_val words; the whole histogram stays
+// in LDS while that fits the words the counts alone may take (lds_words: VPIC_HIP_DIST_LDS_BINS, 32 KB -- the budget of
+// the histogram's LDS path: five workgroups of four wavefronts to a CU's 160 KB, which is the 5 waves per SIMD the
+// instances without field factors reach by their registers; those with them reach 3, profiles/dist_sums_resources.txt -- so
+// LDS never lowers the occupancy).  Everything larger adds in global memory: the sums have no sliding window.
+struct DistSumsPlan { int path = DIST_LDS; long long words = 0; };           // words: 32-bit LDS words (0 for DIST_GLOBAL)
+inline DistSumsPlan plan_distribution_sums(long long bins, int n_val, int lds_words) {
+  DistSumsPlan pl;
+  const long long words = bins * (1 + 2 * (long long)n_val);
+  if (words <= lds_words) pl.words = words; else pl.path = DIST_GLOBAL;
+  return pl;
+}
+
 // DIST_WINDOW on a species in tile order: which particles a wavefront takes.  All tiles with the same tile index along
 // the position axis (a "column") touch the same few bins of it, so a wavefront that takes `group` tiles of ONE column
 // moves its window once and flushes it once for all of them -- a flush adds every non-zero word of the window to global

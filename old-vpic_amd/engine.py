@@ -61,6 +61,18 @@ FIELD_COORDS = {"u_par": 16, "u_perp": 17, "cos_pitch": 18, "mu": 19, "b": 20, "
 DIST_MAX_BINS, DIST_LDS_BINS = 1 << 22, 8192                                                   # VPIC_HIP_DIST_*
 
 
+class DistValue(C.Structure):
+    """vpic_hip_dist_value_t (include/vpic_hip.h): val = (f0 * f1) * f2 in units of quantum"""
+    _fields_ = [("factor", C.c_int32 * 3), ("pad", C.c_int32), ("quantum", C.c_double)]
+
+
+assert C.sizeof(DistValue) == 24
+# the factors of a per-bin sum beyond the coordinates (VPIC_HIP_FACTOR_*); "log10_ke" is an axis and a range only
+VALUE_FACTORS = {"one": 32, "q": 33, "edotv": 34, "epar_vpar": 35}
+DIST_MAX_VALUES = 4                                                                            # VPIC_HIP_DIST_MAX_VALUES
+DistSums = collections.namedtuple("DistSums", "counts isums sums refused")
+
+
 class SelectDesc(C.Structure):
     """vpic_hip_select_t (include/vpic_hip.h)"""
     _fields_ = [("n_sel", C.c_int32), ("flags", C.c_int32), ("sel", DistRange * 4),
@@ -93,6 +105,25 @@ def dist_desc(axes, select=()):
         d.axis[k] = DistAxis(_coord(coord), int(n), float(lo), float(width))
     _set_ranges(d, select)
     return d
+
+
+def _factor(name):
+    """VPIC_HIP_FACTOR_* or VPIC_HIP_COORD_* of a factor's name (KeyError for an unknown one; "log10_ke" is passed on and
+    refused by the library)"""
+    return VALUE_FACTORS[name] if name in VALUE_FACTORS else _coord(name)
+
+
+def dist_values(values):
+    """vpic_hip_dist_value_t[n] of one to four ((factor, ...), quantum) values, one to three factors each by name"""
+    values = list(values)
+    if not 1 <= len(values) <= DIST_MAX_VALUES or any(not 1 <= len(f) <= 3 for f, _ in values):
+        raise ValueError("distribution_sums: one to four values of one to three factors each")
+    v = (DistValue * len(values))()
+    for k, (factors, quantum) in enumerate(values):
+        codes = [_factor(name) for name in factors]
+        codes += [VALUE_FACTORS["one"]] * (3 - len(codes))
+        v[k] = DistValue((C.c_int32 * 3)(*codes), 0, float(quantum))
+    return v
 
 
 def select_desc(select=(), tag_range=None, tag_every=None):
@@ -422,6 +453,34 @@ class Engine:
         out = (C.c_int64 * 4)()
         self._ck(self._l.vpic_hip_species_distribution_stats(self._h, out))
         return tuple(int(v) for v in out)
+
+    def distribution_sums(self, sp, axes, values, select=()):
+        """DistSums(counts, isums, sums, refused): beside the histogram of `distribution` (counts, the same bit for bit),
+        per-bin sums of up to four values over the particles counted.  values: ((factor, ...), quantum) each, one to three
+        factors whose product is the particle's value: a coordinate of `distribution` other than "log10_ke", "one",
+        "q" (the particle's macro-charge, its weight), "edotv" (E . u / gamma) or "epar_vpar" (e_par u_par / gamma).
+        isums int64[n_val, n0] or [n_val, n1, n0]: the sum of rint(value / quantum), exact integers -- the same in every
+        order of the array and additive across ranks; sums = isums * quantum (float64); refused int64[n_val]: particles
+        whose |value / quantum| is 2^32 or more or NaN, which add nothing to that value."""
+        d = dist_desc(axes, select)
+        v = dist_values(values)
+        n0, n1 = max(d.axis[0].n, 0), max(d.axis[1].n, 0) if d.n_axes == 2 else 1
+        bins = min(n0 * n1, DIST_MAX_BINS)                               # (a descriptor the library refuses is refused below)
+        counts = np.zeros(bins, np.uint64)
+        isums = np.zeros((len(v), bins), np.int64)
+        self._ck(self._l.vpic_hip_species_distribution_sums(self._h, int(sp), C.byref(d), v, len(v), _ptr(counts) if bins else None,
+                                                            _ptr(isums) if bins else None))
+        shape = (n1, n0) if d.n_axes == 2 else (n0,)
+        isums = isums.reshape((len(v),) + shape)
+        quanta = np.array([x.quantum for x in v]).reshape((len(v),) + (1,) * len(shape))
+        return DistSums(counts.reshape(shape), isums, isums * quanta, np.array(self.distribution_sums_stats()[4:4 + len(v)], np.int64))
+
+    def distribution_sums_stats(self):
+        """(live particles seen, kept by the selection, counted, added through global memory, refused for value 0, 1, 2, 3)
+        of the last distribution_sums call."""
+        out = (C.c_int64 * 8)()
+        self._ck(self._l.vpic_hip_species_distribution_sums_stats(self._h, out))
+        return tuple(int(x) for x in out)
 
     # ---- selected particles (include/vpic_hip.h: vpic_hip_species_select) ----
     def select_count(self, sp, select=(), tag_range=None, tag_every=None):

@@ -598,14 +598,11 @@ void vpic_simulation::energy_spectrum(species_t *sp, int nex, double dke, float 
     for (int k = 0; k < nbin; k++) spectrum[k] = (float)counts[k];
   }
 }
-void vpic_simulation::distribution(species_t *sp, const vpic_hip_dist_t *d, uint64_t *counts) {
-  if (!sp) ERROR(("Invalid species"));
-  if (!d || !counts) ERROR(("Invalid distribution arguments"));
-  const int id = resident_id(sp->p);
-  if (!engine || id < 0) ERROR(("distribution before the run has started is not supported by this host"));
+// a deck's histogram for the engine: position axes and ranges from physical units to cells of this domain
+static vpic_hip_dist_t distribution_in_cells(const vpic_hip_dist_t &d, const grid_t *grid) {
   const double origin[3] = {(double)grid->x0, (double)grid->y0, (double)grid->z0};
   const double cell[3] = {(double)grid->dx, (double)grid->dy, (double)grid->dz};
-  vpic_hip_dist_t local = *d;                               // position axes and ranges: physical units -> cells of this domain
+  vpic_hip_dist_t local = d;
   for (int a = 0; a < 2; a++) {
     vpic_hip_dist_axis_t &x = local.axis[a];
     if (x.coord < VPIC_HIP_COORD_X || x.coord > VPIC_HIP_COORD_Z) continue;
@@ -618,7 +615,24 @@ void vpic_simulation::distribution(species_t *sp, const vpic_hip_dist_t *d, uint
     r.lo = (r.lo - origin[r.coord]) / cell[r.coord];
     r.hi = (r.hi - origin[r.coord]) / cell[r.coord];
   }
+  return local;
+}
+void vpic_simulation::distribution(species_t *sp, const vpic_hip_dist_t *d, uint64_t *counts) {
+  if (!sp) ERROR(("Invalid species"));
+  if (!d || !counts) ERROR(("Invalid distribution arguments"));
+  const int id = resident_id(sp->p);
+  if (!engine || id < 0) ERROR(("distribution before the run has started is not supported by this host"));
+  const vpic_hip_dist_t local = distribution_in_cells(*d, grid);
   CK(vpic_hip_species_distribution(engine, id, &local, counts));
+}
+void vpic_simulation::distribution_sums(species_t *sp, const vpic_hip_dist_t *d, const vpic_hip_dist_value_t *v, int n_val,
+                                        uint64_t *counts, int64_t *sums) {
+  if (!sp) ERROR(("Invalid species"));
+  if (!d || !v || !sums) ERROR(("Invalid distribution_sums arguments"));
+  const int id = resident_id(sp->p);
+  if (!engine || id < 0) ERROR(("distribution_sums before the run has started is not supported by this host"));
+  const vpic_hip_dist_t local = distribution_in_cells(*d, grid);   // (the factors pass through: engine units)
+  CK(vpic_hip_species_distribution_sums(engine, id, &local, v, n_val, counts, sums));
 }
 // a deck's selection for the engine: position ranges from physical units to cells of this domain, as distribution(); every
 // other range -- those in the frame of the local field too -- and the tag conditions as they are

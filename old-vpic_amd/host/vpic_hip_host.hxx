@@ -323,6 +323,16 @@ public:
   // momenta are u, cB and E are in the units the field array holds).  They use the interpolator on the device, which
   // advance() has loaded for the current fields when user_diagnostics runs, and the stored momenta.
   void distribution(species_t *sp, const vpic_hip_dist_t *d, uint64_t *counts);
+  // The same histogram with up to four per-bin sums of particle quantities beside it, as exact integers
+  // (vpic_hip_species_distribution_sums, include/vpic_hip.h: the factors, the arithmetic, the quantum, the refusals;
+  // sums[k * n0*n1 + b1*n0 + b0], counts may be NULL).  Axes and ranges are in PHYSICAL units, converted exactly as
+  // distribution() converts them.  The FACTORS pass through in engine units: momenta are u, VPIC_HIP_FACTOR_Q is the
+  // particle's q as stored, E and cB are in the units the field array holds -- and a position used as a factor is in LOCAL
+  // CELLS of this rank's domain (it has no origin), so a deck that wants a moment in x forms it from the bins.  This rank's
+  // particles only: int64 sums of several ranks add exactly, in any order (MPI_SUM over MPI_INT64_T), as the counts do.
+  // A particle refused for a value (|value / quantum| >= 2^32, or NaN) is reported by vpic_hip_species_distribution_sums_stats,
+  // not by this call.  The particle mirror does not become resident.  Only once the run has started.
+  void distribution_sums(species_t *sp, const vpic_hip_dist_t *d, const vpic_hip_dist_value_t *v, int n_val, uint64_t *counts, int64_t *sums);
   // The particles of a species inside up to four ranges and with the tags asked for, from the resident state, in place of
   // a loop over sp->p that tests every particle (vpic_hip_species_select, include/vpic_hip.h: the descriptor, the order,
   // the arithmetic of the fields).  Returns how many particles are kept; the first min(that, cap) of them are written, in
