@@ -436,6 +436,81 @@ int vpic_hip_species_distribution_sums(vpic_hip_engine_t *e, int sp, const vpic_
  *     and out[3] == out[2].  (There is no sliding window for sums: a position axis makes no difference.) */
 int vpic_hip_species_distribution_sums_stats(vpic_hip_engine_t *e, int64_t out[8]);
 
+/* ---- cell distributions: the histogram and the exact per-bin sums above, over the CELLS OF THE GRID instead of the
+ * particles of a species (csrc/cell_dist.hip, csrc/cell_coords.h) ----
+ * The descriptors are vpic_hip_dist_t and vpic_hip_dist_value_t unchanged: 1 or 2 axes, 0 to 4 ranges lo <= c < hi,
+ * val = (f0 * f1) * f2 in units of quantum.  Their coord and factor codes are the VPIC_HIP_CELL_* below, numbered from 64
+ * so that no particle code (VPIC_HIP_COORD_*, VPIC_HIP_FACTOR_*) is one of them: a particle code is an unknown coordinate.
+ * Items: the nx * ny * nz interior cells, 1 <= cx <= nx, 1 <= cy <= ny, 1 <= cz <= nz, voxel v = cx + sy * (cy + (ny+2) * cz),
+ *   sy = nx + 2, sz = sy * (ny + 2).  A ghost voxel is never an item (and is read only as the +1 neighbour of an interior cell:
+ *   every read is inside the array).
+ * Per cell:
+ *   X, Y, Z     the cell's centre in local cells: X = (double)(cx - 1) + 0.5, Y and Z likewise.  An axis lo = 0, d = 1,
+ *               n = nx has one bin per column of cells, exactly.
+ *   F_EX .. F_RHOF (VPIC_HIP_CELL_F0 + word)   the 16 float words of vpic_field_t at voxel v, in its order, promoted to
+ *               double; each at its own place on the Yee mesh, attributed to cell v.
+ *   H_JX .. H_TXY (VPIC_HIP_CELL_H0 + word)    the 14 float words of the engine's hydro record (vpic_hydro_t) at voxel v --
+ *               node values -- promoted to double.  A descriptor that names one fails when the hydro array was never
+ *               allocated (nothing has cleared, set, read or accumulated it).
+ *   Cell-centre fields from the FIELD ARRAY, in float, every operation rounded once, unfused, the expressions of
+ *   load_interpolator (src/sf_interface/load_interpolator.cxx:75-120):
+ *     EX_C = 0.25f * ((w3 + w0) + (w1 + w2))   w0 = ex[v], w1 = ex[v+sy], w2 = ex[v+sz], w3 = ex[v+sy+sz]
+ *     EY_C   the same over                      ey[v], ey[v+sz], ey[v+1], ey[v+sz+1]
+ *     EZ_C   the same over                      ez[v], ez[v+1], ez[v+sy], ez[v+1+sy]
+ *     BX_C = 0.5f * (cbx[v+1] + cbx[v])         BY_C pairs v with v+sy, BZ_C with v+sz
+ *     JX_C, JY_C, JZ_C   the expressions of EX_C, EY_C, EZ_C over jfx, jfy, jfz
+ *   then promoted to double as Ex, Ey, Ez, Bx, By, Bz, Jx, Jy, Jz.  Of a freshly loaded interpolator EX_C .. BZ_C equal
+ *   ex, ey, ez, cbx, cby, cbz of the cell's record bit for bit; the call reads the field array, never the interpolator,
+ *   so they are never stale.
+ *   Derived, IEEE double, every operation rounded once, unfused, summed from the left:
+ *     E_C     = sqrt((Ex*Ex + Ey*Ey) + Ez*Ez)          B_C = sqrt((Bx*Bx + By*By) + Bz*Bz)
+ *     E_PAR_C = ((Ex*Bx + Ey*By) + Ez*Bz) / B_C        J_PAR_C = ((Jx*Bx + Jy*By) + Jz*Bz) / B_C
+ *     JDOTE_C = (Jx*Ex + Jy*Ey) + Jz*Ez
+ *   No special cases: B_C == 0 gives NaN for E_PAR_C and J_PAR_C.  A NaN lies in no bin and in no range.
+ *   ONE         1.0; a factor only (as an axis or a range it is an unknown coordinate).
+ * Selection, bins, values and refusals are vpic_hip_species_distribution_sums' word for word: a cell is kept when
+ * lo <= c < hi for every range; per axis t = (c - lo) / d, a kept cell is counted when t >= 0 && t < n on every axis, in bin
+ * (int)t, nothing clamped; value k of a counted cell, t = val / quantum, adds llrint(t) to its bin of sums[k] when
+ * fabs(t) < 4294967296.0 and otherwise (a NaN included) is refused for value k alone -- the cell stays counted and the other
+ * values take it.  A grid holds fewer than 2^31 cells: no int64 sum can wrap.  Counts and sums are integers: the same bit
+ * for bit on either path below, and the sums of several ranks add exactly.
+ * Only the component arrays the descriptor names are read (4 bytes per cell and raw word, the two or four neighbour words
+ * of a centred field, 16 bytes per four hydro words).  Fields, hydro, interpolator and every species are left as they were. */
+enum { VPIC_HIP_CELL_X = 64, VPIC_HIP_CELL_Y, VPIC_HIP_CELL_Z,                                /* 64..66 */
+       VPIC_HIP_CELL_F0 = 72,                                                                  /* 72..87: F0 + word of vpic_field_t */
+       VPIC_HIP_CELL_F_EX = 72, VPIC_HIP_CELL_F_EY, VPIC_HIP_CELL_F_EZ, VPIC_HIP_CELL_F_DIV_E_ERR,
+       VPIC_HIP_CELL_F_CBX, VPIC_HIP_CELL_F_CBY, VPIC_HIP_CELL_F_CBZ, VPIC_HIP_CELL_F_DIV_B_ERR,
+       VPIC_HIP_CELL_F_TCAX, VPIC_HIP_CELL_F_TCAY, VPIC_HIP_CELL_F_TCAZ, VPIC_HIP_CELL_F_RHOB,
+       VPIC_HIP_CELL_F_JFX, VPIC_HIP_CELL_F_JFY, VPIC_HIP_CELL_F_JFZ, VPIC_HIP_CELL_F_RHOF,
+       VPIC_HIP_CELL_H0 = 88,                                                                  /* 88..101: H0 + word of vpic_hydro_t */
+       VPIC_HIP_CELL_H_JX = 88, VPIC_HIP_CELL_H_JY, VPIC_HIP_CELL_H_JZ, VPIC_HIP_CELL_H_RHO,
+       VPIC_HIP_CELL_H_PX, VPIC_HIP_CELL_H_PY, VPIC_HIP_CELL_H_PZ, VPIC_HIP_CELL_H_KE,
+       VPIC_HIP_CELL_H_TXX, VPIC_HIP_CELL_H_TYY, VPIC_HIP_CELL_H_TZZ,
+       VPIC_HIP_CELL_H_TYZ, VPIC_HIP_CELL_H_TZX, VPIC_HIP_CELL_H_TXY,
+       VPIC_HIP_CELL_EX_C = 104, VPIC_HIP_CELL_EY_C, VPIC_HIP_CELL_EZ_C,                       /* 104..112 */
+       VPIC_HIP_CELL_BX_C, VPIC_HIP_CELL_BY_C, VPIC_HIP_CELL_BZ_C,
+       VPIC_HIP_CELL_JX_C, VPIC_HIP_CELL_JY_C, VPIC_HIP_CELL_JZ_C,
+       VPIC_HIP_CELL_E_C = 113, VPIC_HIP_CELL_B_C, VPIC_HIP_CELL_E_PAR_C, VPIC_HIP_CELL_J_PAR_C,
+       VPIC_HIP_CELL_JDOTE_C,                                                                  /* 113..117 */
+       VPIC_HIP_CELL_ONE = 127 };                                                              /* a factor only */
+/* counts: n0 * n1 uint64 in host memory, counts[b1 * n0 + b0], or NULL when n_val > 0; sums: n_val * n0 * n1 int64 in host
+ * memory, sums[k * n0*n1 + b1*n0 + b0]; n_val 0 .. VPIC_HIP_DIST_MAX_VALUES, v and sums may be NULL when it is 0.
+ * Fails (non-zero, vpic_hip_last_error, no output written) on a NULL d, both outputs NULL, a NULL counts with n_val == 0,
+ * n_axes other than 1 or 2, n_sel outside 0..4, an unknown code, n < 1, a d that is not positive and finite, n0 * n1 above
+ * VPIC_HIP_DIST_MAX_BINS, n_val outside 0..VPIC_HIP_DIST_MAX_VALUES, a NULL v or sums with n_val > 0, a quantum that is not
+ * positive and finite, or a hydro code without a hydro array.  Returns 0 when cells were refused: the caller reads the
+ * statistics. */
+int vpic_hip_cell_distribution(vpic_hip_engine_t *e, const vpic_hip_dist_t *d, const vpic_hip_dist_value_t *v, int n_val,
+                               uint64_t *counts, int64_t *sums);
+/* The last call: out[0] cells seen (nx * ny * nz), out[1] cells kept by the ranges, out[2] cells counted (the sum of
+ * counts), out[3] cells counted through global memory, out[4 + k] cells refused for value k (0 for k >= n_val).  Two paths,
+ * with the budget of vpic_hip_species_distribution_sums (cell_dist.hip):
+ *   n0 * n1 * (1 + 2 n_val) <= VPIC_HIP_DIST_LDS_BINS: every workgroup keeps the 32-bit counts and n_val rows of 64-bit
+ *     sums in LDS and adds them to global memory once, at the end; out[3] is 0.
+ *   Larger: every counted cell adds in global memory, the lanes of a wavefront that share a bin combining first, and
+ *     out[3] == out[2].  (No sliding window.) */
+int vpic_hip_cell_distribution_stats(vpic_hip_engine_t *e, int64_t out[8]);
+
 /* ---- selected particles of a species: those inside up to four ranges and with the tags asked for, gathered into dense
  * arrays where the particles are, so that only they come to the host (csrc/select.hip) ----
  * Live particles: 0 <= i < nv; dead slots (i = -1) are skipped, particles appended since the last sort are included.

@@ -102,6 +102,8 @@ def lib():
     L.vpic_hip_species_distribution_stats.argtypes = [C.c_void_p, C.c_void_p]
     L.vpic_hip_species_distribution_sums.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.vpic_hip_species_distribution_sums_stats.argtypes = [C.c_void_p, C.c_void_p]
+    L.vpic_hip_cell_distribution.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.vpic_hip_cell_distribution_stats.argtypes = [C.c_void_p, C.c_void_p]
     L.vpic_hip_moments_stats.argtypes = [C.c_void_p, C.c_void_p]
     L.vpic_hip_species_select_count.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.vpic_hip_species_select.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 4
@@ -127,5 +129,6 @@ vpic_hip_pack_jf vpic_hip_unpack_jf vpic_hip_step vpic_hip_profile_enable vpic_h
 vpic_hip_energy_spectrum vpic_hip_energy_bands vpic_hip_energy_spectrum_stats
 vpic_hip_species_distribution vpic_hip_species_distribution_stats vpic_hip_moments_stats
 vpic_hip_species_distribution_sums vpic_hip_species_distribution_sums_stats
+vpic_hip_cell_distribution vpic_hip_cell_distribution_stats
 vpic_hip_species_select_count vpic_hip_species_select vpic_hip_species_select_stats
 vpic_hip_accumulate_hydro_p_select""".split()

@@ -271,25 +271,7 @@ struct DistSumsK {
   int n0, n1, n_val;
 };
 
-// From this many lanes in the first counted lane's bin on they add their addends up across the wavefront and that lane
-// adds once (a cold beam puts a whole wavefront in one word, and adds to one word are served one after the other); fewer
-// add for themselves, which costs less than the six exchanges of a 64-bit word the adding-up takes per value.
-constexpr int SUMS_TOGETHER_MIN = 8;
-
-// the lanes for which `on` holds add `x` to word[a]; together: those of `same` (the lanes that share lane lead's word)
-// add once
-__device__ __forceinline__ void add_sums_together(unsigned long long *word, int a, long long x, bool on, bool together,
-                                                  unsigned long long same, int lead, int lane) {
-  bool mine = on;
-  if (together) {
-    const bool shared = same >> lane & 1ull;
-    long long s = shared ? x : 0;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-    if (shared) { mine = lane == lead; x = s; }
-  }
-  if (mine && x) atomicAdd(word + a, (unsigned long long)x);                 // (two's complement: the unsigned add is the signed one)
-}
+// (SUMS_TOGETHER_MIN and add_sums_together, which the sums over the cells of the grid use too (cell_dist.hip): engine.h)
 
 // One pass over the species, every wavefront a contiguous chunk, as species_distribution_kernel walks it (the same loads
 // ahead, the same coordinates, the same counted test), plus q when a value names it.

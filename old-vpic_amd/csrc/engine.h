@@ -180,6 +180,27 @@ __device__ __forceinline__ void add_together(T *word, int a, bool on, int lane) 
   }
 }
 
+// ---- ... and the per-bin sums (distribution.hip, cell_dist.hip) ----
+// From this many lanes in the first counted lane's bin on they add their addends up across the wavefront and that lane
+// adds once (a cold beam puts a whole wavefront in one word, and adds to one word are served one after the other); fewer
+// add for themselves, which costs less than the six exchanges of a 64-bit word the adding-up takes per value.
+constexpr int SUMS_TOGETHER_MIN = 8;
+
+// the lanes for which `on` holds add `x` to word[a]; together: those of `same` (the lanes that share lane lead's word)
+// add once
+__device__ __forceinline__ void add_sums_together(unsigned long long *word, int a, long long x, bool on, bool together,
+                                                  unsigned long long same, int lead, int lane) {
+  bool mine = on;
+  if (together) {
+    const bool shared = same >> lane & 1ull;
+    long long s = shared ? x : 0;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+    if (shared) { mine = lane == lead; x = s; }
+  }
+  if (mine && x) atomicAdd(word + a, (unsigned long long)x);                 // (two's complement: the unsigned add is the signed one)
+}
+
 // THE SLIDING WINDOW of a wavefront: `n_slots` consecutive positions (sort keys, bins of a position axis) x `stride` counters
 // in LDS, [slot * stride + offset], from position `base` on.  Per pass of 64 particles the lanes whose position is inside the
 // window add there; if some are not, the window is flushed (flush(base): the caller adds it to global memory and clears it)
@@ -340,6 +361,13 @@ struct Engine {
   // through global memory, refused for value 0 .. 3} on the device, pinned, and as read by the last call
   unsigned long long *dist_sums = nullptr, *dist_sums_host = nullptr; size_t dist_sums_words = 0, dist_sums_host_words = 0;
   unsigned long long *dist_sums_stats = nullptr, *dist_sums_stats_host = nullptr; int64_t dist_sums_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // cell distributions (cell_dist.hip), allocated by the first call and grown on demand: the counters and the n_val rows of
+  // 64-bit sums over the cells of the grid, the pinned buffers they come back through; statistics {seen, kept, counted,
+  // through global memory, refused for value 0 .. 3} on the device, pinned, and as read by the last call (eight words, as
+  // the species' sums keep theirs: a DiagStats holds four)
+  unsigned long long *cell_counts = nullptr, *cell_host = nullptr; size_t cell_bins = 0, cell_host_bins = 0;
+  unsigned long long *cell_sums = nullptr, *cell_sums_host = nullptr; size_t cell_sums_words = 0, cell_sums_host_words = 0;
+  unsigned long long *cell_stats = nullptr, *cell_stats_host = nullptr; int64_t cell_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // hydro moments and rho summed by tile (moments.hip), allocated by the first call: the fixed-point words of the
   // deterministic hydro sums (14 per voxel, zero between calls); statistics {live, through LDS, through global memory, out
   // of range} (mom_stats.pending: the last call's are still on the device, not read yet)
@@ -446,6 +474,8 @@ int k_energy_bands(Engine *e, int n_lin);                                       
 int k_species_distribution(Engine *e, Species &s, const vpic_hip_dist_t &d);     // into Engine::dist_counts / dist_host; waits for the stream
 constexpr int DIST_SUMS_STATS = 8;       // words of Engine::dist_sums_stats
 int k_species_distribution_sums(Engine *e, Species &s, const vpic_hip_dist_t &d, const vpic_hip_dist_value_t *v, int n_val);   // ... and into dist_sums / dist_sums_host
+constexpr int CELL_DIST_STATS = 8;       // words of Engine::cell_stats
+int k_cell_distribution(Engine *e, const vpic_hip_dist_t &d, const vpic_hip_dist_value_t *v, int n_val);   // cell_dist.hip: into Engine::cell_counts / cell_host, cell_sums / cell_sums_host; waits for the stream
 // select.hip: launches 1 and 2 (count_only: no masks), and launch 3 into Engine::sel_p / sel_f / sel_i where asked for; waits for the stream
 int k_species_select(Engine *e, Species &s, const vpic_hip_select_t &d, int64_t cap, bool want_p, bool want_f, bool want_i, bool count_only);
 int k_sort_p(Engine *e, Species &s, bool tile_order = false, bool may_fuse = false);   // may_fuse: the caller pushes the species next (see Species::fuse_pending)

@@ -2,6 +2,7 @@
 // mirror transfers, the per-step driver and HIP-event profiling.  Kernels live in push.hip,
 // fields.hip and particles.hip.
 #include "engine.h"
+#include "cell_coords.h"
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -192,6 +193,8 @@ static void destroy(Engine *e) {
   (void)hipFree(e->acc64); (void)hipFree(e->rho64);
   (void)hipFree(e->spec_lin); (void)hipFree(e->spec_bands); (void)hipFree(e->spec_log); (void)hipHostFree(e->spec_log_host);
   (void)hipFree(e->dist_counts); (void)hipHostFree(e->dist_host); (void)hipFree(e->hydro64);
+  (void)hipFree(e->cell_counts); (void)hipHostFree(e->cell_host); (void)hipFree(e->cell_sums); (void)hipHostFree(e->cell_sums_host);
+  (void)hipFree(e->cell_stats); (void)hipHostFree(e->cell_stats_host);
   (void)hipFree(e->dist_sums); (void)hipHostFree(e->dist_sums_host); (void)hipFree(e->dist_sums_stats); (void)hipHostFree(e->dist_sums_stats_host);
   (void)hipFree(e->sel_mask); (void)hipFree(e->sel_offsets); (void)hipFree(e->sel_counts);
   (void)hipFree(e->sel_p); (void)hipFree(e->sel_f); (void)hipFree(e->sel_i);
@@ -767,6 +770,46 @@ int vpic_hip_species_distribution_sums_stats(vpic_hip_engine_t *e, int64_t out[8
   ENGINE(e);
   if (!out) VH_FAIL("Bad output");
   for (int j = 0; j < DIST_SUMS_STATS; j++) out[j] = e->dist_sums_last[j];
+  return 0;
+}
+// ---- cell distributions (cell_dist.hip): the checks of the two calls above over the VPIC_HIP_CELL_* codes (cell_coords.h) ----
+int vpic_hip_cell_distribution(vpic_hip_engine_t *e, const vpic_hip_dist_t *d, const vpic_hip_dist_value_t *v, int n_val,
+                               uint64_t *counts, int64_t *sums) {
+  ENGINE(e);
+  if (!d) VH_FAIL("Bad cell distribution descriptor");
+  if (!counts && !sums) VH_FAIL("cell distribution: no output array");
+  if (d->n_axes != 1 && d->n_axes != 2) VH_FAIL("cell distribution: %d axes (1 or 2)", d->n_axes);
+  if (check_range_count("cell distribution", d->n_sel)) return 1;
+  long long bins = 1;
+  for (int a = 0; a < d->n_axes; a++) {
+    const vpic_hip_dist_axis_t &x = d->axis[a];
+    if (!cell_known_coord(x.coord)) VH_FAIL("cell distribution: unknown coordinate %d of axis %d", x.coord, a);
+    if (x.n < 1) VH_FAIL("cell distribution: %d bins on axis %d", x.n, a);
+    if (!(x.d > 0) || !std::isfinite(x.d)) VH_FAIL("cell distribution: bin width %g of axis %d", x.d, a);
+    bins *= x.n;                                            // (at most 2^62)
+  }
+  for (int r = 0; r < d->n_sel; r++)
+    if (!cell_known_coord(d->sel[r].coord)) VH_FAIL("cell distribution: unknown coordinate %d of range %d", d->sel[r].coord, r);
+  if (bins > VPIC_HIP_DIST_MAX_BINS) VH_FAIL("cell distribution: %lld bins above the cap of %d", bins, VPIC_HIP_DIST_MAX_BINS);
+  if (n_val < 0 || n_val > VPIC_HIP_DIST_MAX_VALUES) VH_FAIL("cell distribution: %d values (0 to %d)", n_val, VPIC_HIP_DIST_MAX_VALUES);
+  if (n_val == 0 && !counts) VH_FAIL("Bad counts array");
+  if (n_val > 0 && !v) VH_FAIL("Bad values array");
+  if (n_val > 0 && !sums) VH_FAIL("Bad sums array");
+  for (int k = 0; k < n_val; k++) {
+    for (int c = 0; c < 3; c++)
+      if (!cell_known_factor(v[k].factor[c])) VH_FAIL("cell distribution: factor %d of value %d is %d, not a factor", c, k, v[k].factor[c]);
+    if (!(v[k].quantum > 0) || !std::isfinite(v[k].quantum)) VH_FAIL("cell distribution: quantum %g of value %d", v[k].quantum, k);
+  }
+  if (k_cell_distribution(e, *d, v, n_val)) return 1;       // (fails, before it launches, on a hydro code without a hydro array)
+  const size_t count_bytes = sizeof(uint64_t) * (size_t)bins, sum_bytes = count_bytes * (size_t)n_val;
+  if (counts) { host_will_write(counts, count_bytes); memcpy(counts, e->cell_host, count_bytes); }
+  if (n_val > 0) { host_will_write(sums, sum_bytes); memcpy(sums, e->cell_sums_host, sum_bytes); }
+  return 0;
+}
+int vpic_hip_cell_distribution_stats(vpic_hip_engine_t *e, int64_t out[8]) {
+  ENGINE(e);
+  if (!out) VH_FAIL("Bad output");
+  for (int j = 0; j < CELL_DIST_STATS; j++) out[j] = e->cell_last[j];
   return 0;
 }
 static int check_select(const vpic_hip_select_t *s) {

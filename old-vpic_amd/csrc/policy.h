@@ -344,6 +344,14 @@ inline DistSumsPlan plan_distribution_sums(long long bins, int n_val, int lds_wo
   return pl;
 }
 
+// cell_dist.hip: the workgroups of the pass over the interior cells.  A workgroup takes per_group consecutive cells at a
+// time and strides over the rest; as many workgroups as the cells fill, so that a grid of six cells launches one and no
+// workgroup is idle, and 2048 at the most (eight to a CU: 256^3 cells are 32 rounds of each, and the LDS path's final adds
+// to global memory, one per non-empty word and workgroup, stay few beside the cells).
+inline long long plan_cell_groups(long long cells, int per_group) {
+  return std::max(1ll, std::min(2048ll, (cells + per_group - 1) / per_group));
+}
+
 // DIST_WINDOW on a species in tile order: which particles a wavefront takes.  All tiles with the same tile index along
 // the position axis (a "column") touch the same few bins of it, so a wavefront that takes `group` tiles of ONE column
 // moves its window once and flushes it once for all of them -- a flush adds every non-zero word of the window to global

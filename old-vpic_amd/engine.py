@@ -73,6 +73,47 @@ DIST_MAX_VALUES = 4                                                             
 DistSums = collections.namedtuple("DistSums", "counts isums sums refused")
 
 
+# the coordinates and factors of a CELL of the grid (VPIC_HIP_CELL_*, numbered from 64: no particle code is one of them):
+# the cell's centre, the 16 float words of field_t by their member names, the 14 of hydro_t as "hydro.<member>", the fields
+# at the cell's centre, what derives from them, and "one" (a factor only)
+CELL_FIELD_WORDS = ("ex", "ey", "ez", "div_e_err", "cbx", "cby", "cbz", "div_b_err", "tcax", "tcay", "tcaz", "rhob", "jfx", "jfy", "jfz", "rhof")
+CELL_HYDRO_WORDS = ("jx", "jy", "jz", "rho", "px", "py", "pz", "ke", "txx", "tyy", "tzz", "tyz", "tzx", "txy")
+CELL_COORDS = {"x": 64, "y": 65, "z": 66}
+CELL_COORDS.update({name: 72 + w for w, name in enumerate(CELL_FIELD_WORDS)})                  # VPIC_HIP_CELL_F0 + word
+CELL_COORDS.update({"hydro." + name: 88 + w for w, name in enumerate(CELL_HYDRO_WORDS)})       # VPIC_HIP_CELL_H0 + word
+CELL_COORDS.update({name: 104 + k for k, name in enumerate(("ex_c", "ey_c", "ez_c", "bx_c", "by_c", "bz_c", "jx_c", "jy_c", "jz_c"))})
+CELL_COORDS.update({name: 113 + k for k, name in enumerate(("e_c", "b_c", "e_par_c", "j_par_c", "jdote_c"))})
+CELL_FACTORS = {"one": 127}                                                                     # VPIC_HIP_CELL_ONE
+
+
+def cell_dist_desc(axes, select=()):
+    """vpic_hip_dist_t of one or two (coord, lo, d, n) axes and up to four (coord, lo, hi) ranges over the coordinates of a
+    cell, by name (KeyError for an unknown one, "one" included: it is a factor only)."""
+    axes, select = list(axes), list(select)
+    if len(axes) not in (1, 2) or len(select) > 4:
+        raise ValueError("cell_distribution: one or two axes and at most four ranges")
+    d = DistDesc(len(axes), len(select))
+    for k, (coord, lo, width, n) in enumerate(axes):
+        d.axis[k] = DistAxis(CELL_COORDS[coord], int(n), float(lo), float(width))
+    for k, (coord, lo, hi) in enumerate(select):
+        d.sel[k] = DistRange(CELL_COORDS[coord], 0, float(lo), float(hi))
+    return d
+
+
+def cell_dist_values(values):
+    """vpic_hip_dist_value_t[n] of zero to four ((factor, ...), quantum) values, one to three factors each by name: a
+    coordinate of a cell or "one" (KeyError for an unknown one)"""
+    values = list(values)
+    if len(values) > DIST_MAX_VALUES or any(not 1 <= len(f) <= 3 for f, _ in values):
+        raise ValueError("cell_distribution: at most four values of one to three factors each")
+    v = (DistValue * max(len(values), 1))()
+    for k, (factors, quantum) in enumerate(values):
+        codes = [CELL_FACTORS[name] if name in CELL_FACTORS else CELL_COORDS[name] for name in factors]
+        codes += [CELL_FACTORS["one"]] * (3 - len(codes))
+        v[k] = DistValue((C.c_int32 * 3)(*codes), 0, float(quantum))
+    return v, len(values)
+
+
 class SelectDesc(C.Structure):
     """vpic_hip_select_t (include/vpic_hip.h)"""
     _fields_ = [("n_sel", C.c_int32), ("flags", C.c_int32), ("sel", DistRange * 4),
@@ -480,6 +521,38 @@ class Engine:
         of the last distribution_sums call."""
         out = (C.c_int64 * 8)()
         self._ck(self._l.vpic_hip_species_distribution_sums_stats(self._h, out))
+        return tuple(int(x) for x in out)
+
+    # ---- cell distributions (include/vpic_hip.h: vpic_hip_cell_distribution) ----
+    def cell_distribution(self, axes, values=(), select=()):
+        """DistSums(counts, isums, sums, refused) over the nx ny nz interior CELLS of the grid, shaped like distribution_sums:
+        the histogram over one or two axes (coord, lo, d, n) of the cells inside every (coord, lo, hi) range of `select`, and
+        per-bin sums of zero to four values ((factor, ...), quantum).  Coordinates: "x", "y", "z" (the cell's centre in
+        cells: lo 0, d 1, n nx is one bin per column); the words of the field record at the cell's voxel by field_t's member
+        names, "ex" .. "rhof"; those of the hydro record, "hydro.jx" .. "hydro.txy" (the hydro array must exist:
+        clear_hydro, set_hydro or accumulate_hydro_p first); the fields at the cell's centre from the field array as
+        load_interpolator forms them, "ex_c" .. "bz_c", and the current likewise, "jx_c" .. "jz_c"; "e_c", "b_c" (moduli),
+        "e_par_c", "j_par_c" (along B), "jdote_c" (J . E).  A factor is any of them or "one".  Integers throughout: the
+        same on either path, additive across ranks; refused int64[n_val]: cells whose |value / quantum| is 2^32 or more or
+        NaN, which add nothing to that value.  Nothing the engine holds is changed."""
+        d = cell_dist_desc(axes, select)
+        v, n_val = cell_dist_values(values)
+        n0, n1 = max(d.axis[0].n, 0), max(d.axis[1].n, 0) if d.n_axes == 2 else 1
+        bins = min(n0 * n1, DIST_MAX_BINS)                               # (a descriptor the library refuses is refused below)
+        counts = np.zeros(bins, np.uint64)
+        isums = np.zeros((n_val, bins), np.int64)
+        self._ck(self._l.vpic_hip_cell_distribution(self._h, C.byref(d), v if n_val else None, n_val, _ptr(counts) if bins else None,
+                                                    _ptr(isums) if bins and n_val else None))
+        shape = (n1, n0) if d.n_axes == 2 else (n0,)
+        isums = isums.reshape((n_val,) + shape)
+        quanta = np.array([v[k].quantum for k in range(n_val)]).reshape((n_val,) + (1,) * len(shape))
+        return DistSums(counts.reshape(shape), isums, isums * quanta, np.array(self.cell_distribution_stats()[4:4 + n_val], np.int64))
+
+    def cell_distribution_stats(self):
+        """(cells seen, kept by the ranges, counted, counted through global memory, refused for value 0, 1, 2, 3) of the last
+        cell_distribution call."""
+        out = (C.c_int64 * 8)()
+        self._ck(self._l.vpic_hip_cell_distribution_stats(self._h, out))
         return tuple(int(x) for x in out)
 
     # ---- selected particles (include/vpic_hip.h: vpic_hip_species_select) ----

@@ -598,22 +598,23 @@ void vpic_simulation::energy_spectrum(species_t *sp, int nex, double dke, float 
     for (int k = 0; k < nbin; k++) spectrum[k] = (float)counts[k];
   }
 }
-// a deck's histogram for the engine: position axes and ranges from physical units to cells of this domain
-static vpic_hip_dist_t distribution_in_cells(const vpic_hip_dist_t &d, const grid_t *grid) {
+// a deck's histogram for the engine: position axes and ranges from physical units to cells of this domain; x_code: the
+// code of X, with Y and Z behind it (a particle's VPIC_HIP_COORD_X, or a cell's VPIC_HIP_CELL_X)
+static vpic_hip_dist_t distribution_in_cells(const vpic_hip_dist_t &d, const grid_t *grid, int x_code = VPIC_HIP_COORD_X) {
   const double origin[3] = {(double)grid->x0, (double)grid->y0, (double)grid->z0};
   const double cell[3] = {(double)grid->dx, (double)grid->dy, (double)grid->dz};
   vpic_hip_dist_t local = d;
   for (int a = 0; a < 2; a++) {
     vpic_hip_dist_axis_t &x = local.axis[a];
-    if (x.coord < VPIC_HIP_COORD_X || x.coord > VPIC_HIP_COORD_Z) continue;
-    x.lo = (x.lo - origin[x.coord]) / cell[x.coord];
-    x.d = x.d / cell[x.coord];
+    if (x.coord < x_code || x.coord > x_code + 2) continue;
+    x.lo = (x.lo - origin[x.coord - x_code]) / cell[x.coord - x_code];
+    x.d = x.d / cell[x.coord - x_code];
   }
   for (int s = 0; s < 4; s++) {
     vpic_hip_dist_range_t &r = local.sel[s];
-    if (r.coord < VPIC_HIP_COORD_X || r.coord > VPIC_HIP_COORD_Z) continue;
-    r.lo = (r.lo - origin[r.coord]) / cell[r.coord];
-    r.hi = (r.hi - origin[r.coord]) / cell[r.coord];
+    if (r.coord < x_code || r.coord > x_code + 2) continue;
+    r.lo = (r.lo - origin[r.coord - x_code]) / cell[r.coord - x_code];
+    r.hi = (r.hi - origin[r.coord - x_code]) / cell[r.coord - x_code];
   }
   return local;
 }
@@ -633,6 +634,12 @@ void vpic_simulation::distribution_sums(species_t *sp, const vpic_hip_dist_t *d,
   if (!engine || id < 0) ERROR(("distribution_sums before the run has started is not supported by this host"));
   const vpic_hip_dist_t local = distribution_in_cells(*d, grid);   // (the factors pass through: engine units)
   CK(vpic_hip_species_distribution_sums(engine, id, &local, v, n_val, counts, sums));
+}
+void vpic_simulation::cell_distribution(const vpic_hip_dist_t *d, const vpic_hip_dist_value_t *v, int n_val, uint64_t *counts, int64_t *sums) {
+  if (!d || (!counts && !sums)) ERROR(("Invalid cell_distribution arguments"));
+  if (!engine) ERROR(("cell_distribution before the run has started is not supported by this host"));
+  const vpic_hip_dist_t local = distribution_in_cells(*d, grid, VPIC_HIP_CELL_X);   // (every other code passes through: the units the arrays hold)
+  CK(vpic_hip_cell_distribution(engine, &local, v, n_val, counts, sums));
 }
 // a deck's selection for the engine: position ranges from physical units to cells of this domain, as distribution(); every
 // other range -- those in the frame of the local field too -- and the tag conditions as they are

@@ -333,6 +333,18 @@ public:
   // A particle refused for a value (|value / quantum| >= 2^32, or NaN) is reported by vpic_hip_species_distribution_sums_stats,
   // not by this call.  The particle mirror does not become resident.  Only once the run has started.
   void distribution_sums(species_t *sp, const vpic_hip_dist_t *d, const vpic_hip_dist_value_t *v, int n_val, uint64_t *counts, int64_t *sums);
+  // A 1-D or 2-D histogram over the CELLS of this rank's domain with up to four exact per-bin sums beside it, from the
+  // field and hydro arrays on the device, in place of a loop over field(x,y,z) that downloads the whole array
+  // (vpic_hip_cell_distribution, include/vpic_hip.h: the VPIC_HIP_CELL_* codes, the arithmetic, the quantum, the refusals;
+  // counts[b1 * n0 + b0] or NULL beside values, sums[k * n0*n1 + b1*n0 + b0], n_val 0 to 4).  Axes and ranges over
+  // VPIC_HIP_CELL_X, _Y, _Z are in PHYSICAL units -- the cell's centre, grid->x0 + (cx - 0.5) grid->dx -- converted exactly as
+  // distribution() converts them; every other code is in the units the arrays hold, and a position used as a FACTOR is in
+  // local cells.  The hydro codes read the hydro array as the last hydro_dump / dump_hydro left it.  The field array is the
+  // device's: what a hook has written to `field` reaches it when the hook returns.  This rank's cells only: every rank bins
+  // against the same physical edges, and int64 sums of several ranks add exactly, in any order (MPI_SUM over MPI_INT64_T),
+  // as the counts do.  Cells refused for a value are reported by vpic_hip_cell_distribution_stats.  No mirror becomes
+  // resident.  Only once the run has started.
+  void cell_distribution(const vpic_hip_dist_t *d, const vpic_hip_dist_value_t *v, int n_val, uint64_t *counts, int64_t *sums);
   // The particles of a species inside up to four ranges and with the tags asked for, from the resident state, in place of
   // a loop over sp->p that tests every particle (vpic_hip_species_select, include/vpic_hip.h: the descriptor, the order,
   // the arithmetic of the fields).  Returns how many particles are kept; the first min(that, cap) of them are written, in
