@@ -138,6 +138,7 @@ constexpr int TILE_CELLS = TILE_EDGE * TILE_EDGE * TILE_EDGE;
 struct TileK {
   int sy, sz, ntx, nty, ntz, ntiles;
   unsigned mul_sy, sh_sy, mul_sz, sh_sz;     // magic_div of the voxel strides
+  int mx, my, mz;                            // the last interior cell of every axis, from 0 (nx - 1, ny - 1, nz - 1)
 };
 TileK make_tile_k(const GridK &g);
 
@@ -157,8 +158,9 @@ __device__ __forceinline__ int sort_key(int voxel, const TileK &t) {
   int cx, cy, cz;
   voxel_cell(voxel, t, cx, cy, cz);
   // particles live in interior voxels (1..n); an index in a ghost layer (the reference's sort_p takes any voxel) is
-  // counted with the nearest interior cell's tile instead of indexing outside the tables
-  const int x = min(max(cx - 1, 0), 4 * t.ntx - 1), y = min(max(cy - 1, 0), 4 * t.nty - 1), z = min(max(cz - 1, 0), 4 * t.ntz - 1);
+  // counted with the nearest interior cell instead of indexing outside the tables (the nearest cell that EXISTS: up to
+  // the grid's last cell, not the last tile's -- a partial tile's cells beyond the grid hold nothing in any order)
+  const int x = min(max(cx - 1, 0), t.mx), y = min(max(cy - 1, 0), t.my), z = min(max(cz - 1, 0), t.mz);
   const int tile = ((z >> 2) * t.nty + (y >> 2)) * t.ntx + (x >> 2);
   return tile * TILE_CELLS + ((z & 3) << 4 | (y & 3) << 2 | (x & 3));
 }
@@ -464,7 +466,7 @@ int k_face_count(const Engine *e, int dir);
 int k_pack_face(Engine *e, int dir, float *buf, int what);       // what: 0 tang_b, 1 jf
 int k_unpack_face(Engine *e, int dir, const float *buf, int what);
 
-int k_particles_from_aos(Engine *e, Species &s, const vpic_particle_t *host, int64_t n_new, int64_t at = 0);
+int k_particles_from_aos(Engine *e, Species &s, const vpic_particle_t *host, int64_t n_new, int64_t at = 0, bool any_voxel = false);   // any_voxel: ghost voxels pass too (a test hook's: such a species may be sorted, never pushed)
 int k_particles_to_aos(Engine *e, Species &s, vpic_particle_t *host, int64_t cap, int64_t from = 0, int64_t count = -1);
 int k_load_maxwellian(Engine *e, Species &s, int ppc, unsigned seed, float q, float ux, float uy, float uz, float vth);
 int k_energy_p(Engine *e, Species &s, double *energy);

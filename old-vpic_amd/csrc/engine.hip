@@ -506,6 +506,15 @@ int vpic_hip_debug_poke_tile_max(vpic_hip_engine_t *e, int sp, unsigned value) {
   e->species[sp].crossed_host[PW_FULLEST_TILE] = value;
   return 0;
 }
+// test hook (not part of include/vpic_hip.h): vpic_hip_species_set_particles for particles in ANY voxel of the grid, ghost layers
+// included -- the reference's sort_p takes them and the sort's kernels have a rule for them (engine.h: sort_key), which no
+// particle that came in through the ABI can reach.  Such a species may be sorted and read back; it must never be pushed.
+int vpic_hip_debug_set_particles_any_voxel(vpic_hip_engine_t *e, int sp, const vpic_particle_t *p, int64_t np) {
+  ENGINE(e); SPECIES(e, sp);
+  if (np < 0 || (np > 0 && !p)) VH_FAIL("Bad particle array");
+  host_will_read(p, sizeof(*p) * (size_t)np);
+  return k_particles_from_aos(e, e->species[sp], p, np, 0, true);
+}
 int vpic_hip_species_get_tile_partition(vpic_hip_engine_t *e, int sp, int32_t *tpart, int64_t *count) {
   ENGINE(e); SPECIES(e, sp);
   Species &s = e->species[sp];

@@ -52,13 +52,14 @@ static int ensure_tags(Engine *e, Species &s) {
 }
 
 // host[0..n) -> particles [at, at+n) of the species; at = 0 replaces the list, at = np appends to it
-int k_particles_from_aos(Engine *e, Species &s, const vpic_particle_t *host, int64_t n_new, int64_t at) {
+int k_particles_from_aos(Engine *e, Species &s, const vpic_particle_t *host, int64_t n_new, int64_t at, bool any_voxel) {
   const int64_t np = at + n_new;
   if (np > s.max_np) VH_FAIL("species particles: np=%lld exceeds max_np=%lld", (long long)np, (long long)s.max_np);
   {                                                       // a particle outside the interior voxels would send the push out of bounds
     const GridK &g = e->gk;
     for (int64_t k = 0; k < n_new; k++) {
       const int v = host[k].i, z = v / g.sz, r = v - z * g.sz, y = r / g.sy, x = r - y * g.sy;
+      if (any_voxel && v >= 0 && v < g.nv) continue;        // (inside the sort's tables all the same)
       if (v < 0 || (unsigned)(x - 1) >= (unsigned)g.nx || (unsigned)(y - 1) >= (unsigned)g.ny || (unsigned)(z - 1) >= (unsigned)g.nz)
         VH_FAIL("particle %lld is not in an interior voxel (i = %d)", (long long)k, v);
     }
@@ -174,6 +175,7 @@ TileK make_tile_k(const GridK &g) {
   t.sy = g.sy; t.sz = g.sz;
   t.ntx = (g.nx + TILE_EDGE - 1) / TILE_EDGE; t.nty = (g.ny + TILE_EDGE - 1) / TILE_EDGE; t.ntz = (g.nz + TILE_EDGE - 1) / TILE_EDGE;
   t.ntiles = t.ntx * t.nty * t.ntz;
+  t.mx = g.nx - 1; t.my = g.ny - 1; t.mz = g.nz - 1;
   magic_div((unsigned)g.sy, t.mul_sy, t.sh_sy);
   magic_div((unsigned)g.sz, t.mul_sz, t.sh_sz);
   return t;

@@ -762,6 +762,7 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
     hk.hist = P.hist; hk.s_cnt = s_cnt;
     hk.tk.sy = P.sy; hk.tk.sz = P.sz; hk.tk.ntx = P.ntx; hk.tk.nty = P.nty; hk.tk.ntz = P.ntz; hk.tk.ntiles = P.ntiles;
     hk.tk.mul_sy = P.mul_sy; hk.tk.sh_sy = P.sh_sy; hk.tk.mul_sz = P.mul_sz; hk.tk.sh_sz = P.sh_sz;
+    hk.tk.mx = P.nx - 1; hk.tk.my = P.ny - 1; hk.tk.mz = P.nz - 1;
   }
 
   // STAGE: the waiting passes' positions (slot 0, 1) and how many wait

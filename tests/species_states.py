@@ -44,10 +44,11 @@ def run_child(script, args, timeout):
     assert "child OK" in r.stdout
 
 
-def build_state(V, state, p, grid, tail, dt, doomed_dx):
+def build_state(V, state, p, grid, tail, dt, doomed_dx, coarse=False):
     """(engine, species) with particles p in the array state asked for.  tail: the N_TAIL particles appended in
     "tile_tail_holes" (not looked at otherwise); dt: the step of that state's one push; doomed_dx: the offset of the
-    N_DOOMED particles on their way through the absorbing +x wall (ux = 3)."""
+    N_DOOMED particles on their way through the absorbing +x wall (ux = 3).  coarse: the caller has set
+    VPIC_HIP_TILE_COARSE=1, so every tile sort is by tile only whatever the state (test_gpu_sort.py)."""
     L = V.layout
     nx, ny, nz = grid
     n = len(p)
@@ -72,7 +73,7 @@ def build_state(V, state, p, grid, tail, dt, doomed_dx):
         e.set_sort_order("engine")
         e.sort_p(sp)
         assert e.species_order(sp) == "tile"
-        assert e.species_stats(sp)["by_tile_only"] == (1 if state == "tile_only" else 0)
+        assert e.species_stats(sp)["by_tile_only"] == (1 if state == "tile_only" or coarse else 0)
     if holes:
         assert len(tail) == N_TAIL
         e.append_particles(sp, tail)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import bits_equal
+from sort_ref import _records
 
 pytestmark = pytest.mark.gpu
 ACC_TOL = 2e-6
@@ -331,12 +332,6 @@ def test_the_push_before_a_sort_counts_for_it(V, orc, L, case):
     e.sort_p(sp)                                            # counts for itself: same cells in the same places
     again = e.get_particles(sp)
     assert np.array_equal(again["i"], got["i"])
-
-
-def _records(p):
-    """particle records without tags, in one canonical order (bit patterns, every field a sort key)"""
-    a = np.stack([p[n].view(np.uint32) for n in ("i", "dx", "dy", "dz", "ux", "uy", "uz", "q")], axis=1)
-    return a[np.lexsort(a.T[::-1])]
 
 
 @pytest.mark.parametrize("case", ["cold_beams", "hot", "reflecting_z"])
