@@ -237,7 +237,24 @@ int vpic_hip_set_push_mode(vpic_hip_engine_t *e, int mode);
  * HBM, so accumulators, jf, rhof and everything downstream are bit-identical from run to run whatever the array order,
  * the scheduling or the order messages arrive in.  The reference is reproducible by construction (private accumulators
  * reduced in a fixed order, sf_interface/reduce_accumulators.cxx:37-55); this mode is how the engine gets there.  Particle
- * results are the same in both modes.  Costs the cold decks their in-register run sums (every lane adds for itself).
+ * results are the same in both modes.
+ * THE RULE of the push's deposits, a contract (tests/test_gpu_det_exact.py holds every word of the accumulator to it, on
+ * every instance of advance_p and on the injection path; oracle/vpic_oracle.h, orc_set_fixed_accumulator, and pyorc.fixed_scale
+ * / finalize are its CPU restatement, pinned on the compiled reference by tests/test_det_ref.py):
+ *   - the scale is the power of two  scale = 2^(37 - ex),  4.2 q = m 2^ex with 0.5 <= m < 1 (frexp),  where q is q_ref when
+ *     q_ref > 0 and otherwise the largest |q| the host has put into any species so far (set / appended / injected particles) at
+ *     the moment the first deterministic kernel after this call adds; it then stays until the next vpic_hip_set_accumulation;
+ *   - each of the 12 floats v of each straight streak -- formed operation by operation as the reference's scalar code forms them
+ *     (advance_p.cxx:131-162 for a particle that stays in its cell, move_p.c:76-100 for every segment of one that does not,
+ *     its v5 with the last multiply in double), uncontracted, in either push mode -- becomes the integer rint(v * scale),
+ *     to nearest even (v * scale is exact in double), and is added to the 64-bit word of its voxel and component;
+ *   - reading the accumulator (or unloading it) rounds each word once, float((double)word * (1 / scale)), and ADDS it to the
+ *     float accumulator, which clear_accumulators zeroes: a word whose sum is zero leaves +0.0 there.  (int64 -> double rounds
+ *     above 2^53: two roundings there.)
+ *   Which instance pushes a species, the order of its array, the windows, the tail, stale tiles: none of them changes a word.
+ *   Range: |v * scale| < 2^51 per deposit (the largest deposit a macro-particle makes, 4.2 |q|, stays below it up to
+ *   |q| = 2^14 q_ref) and at most 2^26 deposits of the reference size per word; beyond it the conversion wraps silently.
+ *   No lower limit: charges far below q_ref lose resolution (a quantum is 2^-37 of 4.2 q_ref), nothing else.
  * The hydro moments join the guarantee: accumulate_hydro_p sums every one of a particle's 8 x 14 contributions as a 64-bit
  * fixed-point integer too (one power-of-two scale per moment and call, from the species' largest macro-particle charge, its
  * q_m, the cell volume and c: policy.h, moment_scales) and rounds each sum once into the float array, so two runs write the

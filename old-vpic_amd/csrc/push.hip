@@ -268,36 +268,19 @@ __device__ __forceinline__ void run_deposit(float (&a)[12], int key, int lane, t
 // the window by itself (64-bit fixed point, ds_add_u64): on a cell-sorted species the 64 lanes of a pass hit two or three
 // cells -- twenty-fold collisions on every one of the twelve atomics, a launch twice as long as the float mode's.  Integer sums
 // do not care about their order, so the float mode's structure carries over: the lanes regrouped by cell, a segmented scan over
-// each run of equal cells, the run's last lane adding its total.  The scan runs on 32-BIT fixed point (a third of the
-// instructions of a 64-bit one): a deposit is rounded to 2^-26 of the largest one a particle of the reference charge makes
-// (4.2 q_ref -- the 64-bit conversion keeps 2^-37; the float mode's own sums carry 2^-24 of their size), a run of sixteen stays
-// below 2^30.  A pass in which some deposit is too large for that (a macro-particle of more than 1.9 reference charges) adds lane
-// by lane as before: the same integers either way, so the sums do not depend on which path a pass took.
-constexpr int DET_SHIFT = 11;                                    // 32-bit sums are 2^11 coarser than the window's 64-bit words
+// each run of equal cells, the run's last lane adding its total.  The scan sums the SAME 64-bit integers every other
+// deterministic path adds (to_fixed: 2^-37 of the largest deposit a particle of the reference charge makes), as two 32-bit
+// halves per DPP move: the sums must not depend on which instance pushed a species -- the policy may change it from one launch
+// to the next -- and tests/test_gpu_det_exact.py predicts every word of them.  (Round 4 scanned 32-bit integers 2^11 coarser: a
+// third of the instructions, and an in-cell deposit then rounded differently in det_tile than in det_tile_only, det_row and the
+// drain.)  A run of sixteen deposits below 2^51 stays below 2^55.
 template <int BLOCK, class W>
 __device__ __forceinline__ void run_deposit_fixed(const float (&a)[12], int key, int lane, typename W::acc_t *s_acc, float *g_acc,
                                                   int wbase, int sy, int sz, const TileDiv &td, MissList *ml, int &n_miss) {
-  static_assert(BLOCK == 16, "runs of at most 16 lanes: 16 x 2^26 < 2^31");
-  const float s32 = (float)(td.scale * (1.0 / (1 << DET_SHIFT)));          // a power of two: the product below is exact
-  float big = fmaxf(fmaxf(fmaxf(fabsf(a[0]), fabsf(a[1])), fmaxf(fabsf(a[2]), fabsf(a[3]))), fmaxf(fmaxf(fabsf(a[4]), fabsf(a[5])), fmaxf(fabsf(a[6]), fabsf(a[7]))));
-  big = fmaxf(big, fmaxf(fmaxf(fabsf(a[8]), fabsf(a[9])), fmaxf(fabsf(a[10]), fabsf(a[11]))));
-  if (__ballot(key >= 0 && !(big * s32 < 67108864.f))) {       // (wave-uniform, rare; NaNs take this path too)
-    // every lane for itself, rounded the same way: round(a * 2^k) * 2^11
-    if (key >= 0) {
-      const int slot = slot_of<W>(key, wbase, sy, sz, td);
-      unsigned long long *g64 = reinterpret_cast<unsigned long long *>(g_acc) + (size_t)key * 12;
+  static_assert(BLOCK == 16, "runs of at most 16 lanes, within a DPP row");
+  unsigned long long v[12];
 #pragma unroll
-      for (int k = 0; k < 12; k++) {
-        const unsigned long long v = (unsigned long long)((long long)__builtin_rint((double)a[k] * (double)s32) << DET_SHIFT);
-        if (slot >= 0) atomicAdd(&s_acc[k * W::NSLOT_PAD + slot], v); else atomicAdd(&g64[k], v);
-      }
-    }
-    asm volatile("" ::: "memory");
-    return;
-  }
-  int v[12];
-#pragma unroll
-  for (int k = 0; k < 12; k++) v[k] = (int)__builtin_rintf(a[k] * s32);
+  for (int k = 0; k < 12; k++) v[k] = to_fixed(a[k], td.scale);
   const int prev = __builtin_amdgcn_update_dpp(-2, key, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
   const unsigned long long heads = __ballot(prev != key) | 0x0001000100010001ull;    // (rows of 16 lanes)
   const unsigned long long below = heads & ((2ull << lane) - 1ull);
@@ -307,11 +290,17 @@ __device__ __forceinline__ void run_deposit_fixed(const float (&a)[12], int key,
     const bool on = d >= step;
 #pragma unroll
     for (int k = 0; k < 12; k++) {
-      const int t = step == 1 ? __builtin_amdgcn_update_dpp(0, v[k], 0x111 /* row_shr:1 */, 0xf, 0xf, true)
-                  : step == 2 ? __builtin_amdgcn_update_dpp(0, v[k], 0x112, 0xf, 0xf, true)
-                  : step == 4 ? __builtin_amdgcn_update_dpp(0, v[k], 0x114, 0xf, 0xf, true)
-                              : __builtin_amdgcn_update_dpp(0, v[k], 0x118, 0xf, 0xf, true);
-      v[k] += on ? t : 0;
+      const int lo = (int)(unsigned)v[k], hi = (int)(unsigned)(v[k] >> 32);
+      const int tl = step == 1 ? __builtin_amdgcn_update_dpp(0, lo, 0x111 /* row_shr:1 */, 0xf, 0xf, true)
+                   : step == 2 ? __builtin_amdgcn_update_dpp(0, lo, 0x112, 0xf, 0xf, true)
+                   : step == 4 ? __builtin_amdgcn_update_dpp(0, lo, 0x114, 0xf, 0xf, true)
+                               : __builtin_amdgcn_update_dpp(0, lo, 0x118, 0xf, 0xf, true);
+      const int th = step == 1 ? __builtin_amdgcn_update_dpp(0, hi, 0x111, 0xf, 0xf, true)
+                   : step == 2 ? __builtin_amdgcn_update_dpp(0, hi, 0x112, 0xf, 0xf, true)
+                   : step == 4 ? __builtin_amdgcn_update_dpp(0, hi, 0x114, 0xf, 0xf, true)
+                               : __builtin_amdgcn_update_dpp(0, hi, 0x118, 0xf, 0xf, true);
+      const unsigned long long t = ((unsigned long long)(unsigned)th << 32) | (unsigned long long)(unsigned)tl;
+      v[k] += on ? t : 0ull;                                       // (two's complement: wraps like the atomics do)
     }
   }
   const bool tail = key >= 0 && ((lane == 63) || ((heads >> ((lane + 1) & 63)) & 1ull));
@@ -320,8 +309,7 @@ __device__ __forceinline__ void run_deposit_fixed(const float (&a)[12], int key,
     unsigned long long *g64 = reinterpret_cast<unsigned long long *>(g_acc) + (size_t)key * 12;
 #pragma unroll
     for (int k = 0; k < 12; k++) {
-      const unsigned long long w = (unsigned long long)((long long)v[k] << DET_SHIFT);
-      if (slot >= 0) atomicAdd(&s_acc[k * W::NSLOT_PAD + slot], w); else atomicAdd(&g64[k], w);
+      if (slot >= 0) atomicAdd(&s_acc[k * W::NSLOT_PAD + slot], v[k]); else atomicAdd(&g64[k], v[k]);
     }
   }
   asm volatile("" ::: "memory");
@@ -374,6 +362,21 @@ __device__ __forceinline__ void streak12_fast(float *a, float q, float dx, float
   a[4] = __builtin_fmaf(v0, xm, v5); a[5] = __builtin_fmaf(v1, xm, -v5); a[6] = __builtin_fmaf(v0, xp, -v5); a[7] = __builtin_fmaf(v1, xp, v5);
   v0 = __builtin_fmaf(-qz, dx, qz); v1 = __builtin_fmaf(qz, dx, qz);
   a[8] = __builtin_fmaf(v0, ym, v5); a[9] = __builtin_fmaf(v1, ym, -v5); a[10] = __builtin_fmaf(v0, yp, -v5); a[11] = __builtin_fmaf(v1, yp, v5);
+}
+
+// The 12 terms of one segment of a cell-crosser in the arithmetic instance W deposits with.  The DETERMINISTIC instances
+// form them as the reference does, operation by operation (push_device.h: streak12; v5 as move_p.c:76 has it, the last
+// multiply in double): every word of their integer sums is then what an order-free computation on the reference's own floats
+// predicts, which tests/test_gpu_det_exact.py checks exactly.  The float instances keep the contracted form: their sums
+// are rounded in an order of the machine's choosing anyway.
+template <class W>
+__device__ __forceinline__ void mover_streak12(float *a, float q, float mx, float my, float mz, float sx, float sy, float sz) {
+  if constexpr (is_det<W>::value) {
+    const float v5 = (float)((double)(q * sx * sy * sz) * (1. / 3.));
+    streak12(a, q, mx, my, mz, sx, sy, sz, v5);
+  } else {
+    streak12_fast(a, q, mx, my, mz, sx, sy, sz);
+  }
 }
 
 // ---- positions that wait for their cell-crossers (round 4) ------------------------------------------------------------
@@ -475,7 +478,7 @@ __device__ __forceinline__ int drain_wave(const ParticlesK &p, WaveQueue *mq, co
       const float s_dispx = m.dispx * v3, s_dispy = m.dispy * v3, s_dispz = m.dispz * v3;
       const float s_midx = dx + s_dispx, s_midy = dy + s_dispy, s_midz = dz + s_dispz;
       float a[12];
-      streak12_fast(a, q, s_midx, s_midy, s_midz, s_dispx, s_dispy, s_dispz);   // (contracted in both modes: see the main pass)
+      mover_streak12<W>(a, q, s_midx, s_midy, s_midz, s_dispx, s_dispy, s_dispz);   // (contracted unless W is deterministic: see the main pass)
       const int key = live ? pi : -1;
       // neighbor[6*i + face] of move_p.c:123, generated from the per-face codes (ops.c:74-97)
       const bool e0 = up0 ? (cx == gnx) : (cx == 1), e1 = up1 ? (cy == gny) : (cy == 1), e2 = up2 ? (cz == gnz) : (cz == 1);
@@ -531,7 +534,7 @@ __device__ __forceinline__ int drain_wave(const ParticlesK &p, WaveQueue *mq, co
         if (__ballot(fin)) {
           float b[12];
           // f = 1: the segment IS the remaining displacement (disp * 1.0f), its midpoint r + disp (move_p.c:65-74)
-          streak12_fast(b, q, dx + m.dispx, dy + m.dispy, dz + m.dispz, m.dispx, m.dispy, m.dispz);
+          mover_streak12<W>(b, q, dx + m.dispx, dy + m.dispy, dz + m.dispz, m.dispx, m.dispy, m.dispz);
           const int fkey = fin ? pi : -1;
           if (fin) {                                        // move_p.c:103-110 with s_disp = disp; type == 3: done
             dx += m.dispx + m.dispx; dy += m.dispy + m.dispy; dz += m.dispz + m.dispz;
@@ -1025,10 +1028,13 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
       }
       if (!CHARGELESS && !(ablate & 1)) {
         const float qd = (incell && active) ? q : 0.f;
-        // The 12 deposit terms with contracted multiply-adds in BOTH arithmetic modes: they are summed in an order of the
-        // machine's choosing anyway (the accumulators agree with the reference's to 2e-6 of the largest entry, not bit for
-        // bit), each term is within an ulp of the reference's, and no particle state depends on them (+1.3 % measured).
-        streak12_fast(a, qd, v0, v1, v2, ux, uy, uz);
+        // The 12 deposit terms with contracted multiply-adds in BOTH arithmetic modes of the float instances: they are summed
+        // in an order of the machine's choosing anyway (the accumulators agree with the reference's to 2e-6 of the largest
+        // entry, not bit for bit), each term is within a few ulp of the reference's, and no particle state depends on them
+        // (+1.3 % measured).  The DETERMINISTIC instances form them as advance_p.cxx:131-162 does, operation by operation:
+        // their sums are exact, and exactly those of the reference's floats (tests/test_gpu_det_exact.py).
+        if constexpr (is_det<W>::value) streak12(a, qd, v0, v1, v2, ux, uy, uz, qd * ux * uy * uz * one_third);
+        else streak12_fast(a, qd, v0, v1, v2, ux, uy, uz);
       } else {
 #pragma unroll
         for (int k = 0; k < 12; k++) a[k] = 0.f;

@@ -288,6 +288,13 @@ class Engine:
         c = np.ascontiguousarray(components, np.int32)
         self._ck(self._l.vpic_hip_emit(self._h, sp, c.ctypes.data_as(C.c_void_p), len(c), n_emit_per_face, ut_perp, ut_para, coef, thresh, seed))
 
+    def inject_aged(self, inj, tags=None):
+        """Appends the injector records inj (particle_injector_t[n], sp_id names the species) and finishes their moves, as
+        boundary_p does for arrivals; tags: int64[n, 2] (tag, tag2) the particles bring along, or None."""
+        inj = self._arr(inj, L.particle_injector_t)
+        t = None if tags is None else np.ascontiguousarray(tags, np.int64).reshape(len(inj), 2)
+        self._ck(self._l.vpic_hip_inject_aged(self._h, _ptr(inj), None if t is None else _ptr(t), len(inj)))
+
     def accumulate_rhob(self, p, q_scale=1.0):
         p = self._arr(p, L.particle_t)
         self._ck(self._l.vpic_hip_accumulate_rhob(self._h, _ptr(p), len(p), q_scale))

@@ -1,6 +1,8 @@
 """ctypes binding of oracle/libvpic_oracle.so (TEST INFRASTRUCTURE, see vpic_oracle.h)."""
+import contextlib
 import ctypes as C
 import importlib
+import math
 import os
 import subprocess
 
@@ -332,10 +334,48 @@ def boundary_p_inject(p, np_, pm, nm, inj, a, g):
     return new_np, nm_c.value
 
 
-def step(f, fi, a, m, species, g, sort=False, clean_e=False, clean_b=False, sync_shared=False):
+# ---- the exact reference of the engine's deterministic accumulation (include/vpic_hip.h: vpic_hip_set_accumulation) ----
+def fixed_scale(q_ref):
+    """The engine's fixed-point scale for reference charge q_ref > 0 (for q_ref <= 0 the engine takes the largest |q| the
+    host has put into any species so far): a power of two that puts a deposit of 4.2 q_ref near 2^37."""
+    return 2.0 ** (37 - math.frexp(4.2 * q_ref)[1])
+
+
+@contextlib.contextmanager
+def fixed_accumulator(g, scale):
+    """While the block runs, advance_p / move_p / boundary_p_inject / child_langmuir also sum every deposit as the integer
+    llrint(v * scale): yields (a64 int64[nv, 12], streaks int32[nv]); the switch is cleared on the way out, always."""
+    a64, streaks = np.zeros((g.nv, 12), np.int64), np.zeros(g.nv, np.int32)
+    lib().orc_set_fixed_accumulator(_p(a64), _p(streaks), C.c_double(scale))
+    try:
+        yield a64, streaks
+    finally:
+        lib().orc_set_fixed_accumulator(None, None, C.c_double(0.0))
+
+
+def finalize(a64, scale):
+    """accumulator_t[nv] of the integer sums a64[nv, 12]: each converted int64 -> double (which rounds above 2^53), times
+    the exact 1 / scale, rounded to float -- what the engine's acc_finalize leaves in a cleared accumulator."""
+    a = (np.ascontiguousarray(a64, np.int64).astype(np.float64) * (1.0 / scale)).astype(np.float32)
+    return np.ascontiguousarray(a.reshape(-1, 12)).view(L.accumulator_t).reshape(-1)
+
+
+def step(f, fi, a, m, species, g, sort=False, clean_e=False, clean_b=False, sync_shared=False, det_scale=None):
     """One vpic_simulation::advance() of a single self-periodic / locally bounded domain
     (src/vpic/advance.cxx:38-214 without emitters, collisions, injection and div cleaning).
-    species: list of dicts {p, np, q_m, pm, partition}.  Returns nothing; arrays updated in place."""
+    species: list of dicts {p, np, q_m, pm, partition}.  Returns nothing; arrays updated in place.
+    det_scale: the step of an engine in deterministic accumulation -- once every species is pushed and its movers are
+    handled, the accumulator is replaced by finalize() of the exact integer sums at that scale."""
+    if det_scale is not None:
+        with fixed_accumulator(g, det_scale) as (a64, _):
+            _push(f, fi, a, species, g, sort)
+            a[:g.nv] = finalize(a64, det_scale)
+    else:
+        _push(f, fi, a, species, g, sort)
+    _fields(f, fi, a, m, species, g, clean_e, clean_b, sync_shared)
+
+
+def _push(f, fi, a, species, g, sort):
     clear_accumulators(a, g)
     for sp in species:
         if sort:
@@ -346,6 +386,9 @@ def step(f, fi, a, m, species, g, sort=False, clean_e=False, clean_b=False, sync
         if sp["nm"]:
             sp["np"], _ = boundary_p_pack(sp["p"], sp["np"], sp["pm"], sp["nm"], k, f, g, sp["nm"])
             sp["nm"] = 0
+
+
+def _fields(f, fi, a, m, species, g, clean_e, clean_b, sync_shared):
     clear_jf(f, g)
     unload_accumulator(f, a, g)
     synchronize_jf_local(f, g)

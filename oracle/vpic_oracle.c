@@ -114,6 +114,27 @@ void orc_unload_accumulator(orc_field_t *f, const orc_accumulator_t *a, const or
 }
 
 /* ------------------------------------------------------------------------------------------
+ * The exact reference of the engine's deterministic accumulation (include/vpic_hip.h, vpic_hip_set_accumulation; this
+ * is the project's own rule, nothing of the reference's).  While the switch is on, every streak that the two deposit
+ * sites below add to the float accumulator is also rounded, float by float, to the integer llrint(v * scale) -- v * scale is
+ * exact in double (a float times a power of two), llrint rounds to nearest even under the default rounding mode -- and
+ * summed in a64[12 * voxel + k], k over jx[0..3], jy[0..3], jz[0..3]; streaks[voxel] counts the streaks.  Integer sums
+ * do not depend on the order of anything.  The float arithmetic is not touched.                                       */
+static int64_t *fx_a64 = 0;
+static int32_t *fx_streaks = 0;
+static double fx_scale = 0;
+void orc_set_fixed_accumulator(int64_t *a64, int32_t *streaks, double scale) {
+  fx_a64 = a64; fx_streaks = streaks; fx_scale = scale;
+}
+static void fixed_add4(int voxel, int k, float v0, float v1, float v2, float v3) {
+  if (!fx_a64) return;
+  int64_t *w = fx_a64 + 12 * (size_t)voxel + k;
+  w[0] += llrint((double)v0 * fx_scale); w[1] += llrint((double)v1 * fx_scale);
+  w[2] += llrint((double)v2 * fx_scale); w[3] += llrint((double)v3 * fx_scale);
+  if (k == 8 && fx_streaks) fx_streaks[voxel]++;
+}
+
+/* ------------------------------------------------------------------------------------------
  * species_advance/standard/move_p.c:20-136.  The neighbor[] lookup of :123 is replaced by the
  * per-face codes of orc_grid_t (same outcome as grid/ops.c:74-97 + join_grid/set_pbc tables). */
 int orc_move_p(orc_particle_t *p0, orc_mover_t *pm, orc_accumulator_t *a0, const orc_grid_t *g) {
@@ -162,9 +183,9 @@ int orc_move_p(orc_particle_t *p0, orc_mover_t *pm, orc_accumulator_t *a0, const
     v2 -= v5;                                                                     \
     v3 += v5;                                                                     \
     a[0] += v0; a[1] += v1; a[2] += v2; a[3] += v3
-    accumulate_j(x, y, z); a += 4;
-    accumulate_j(y, z, x); a += 4;
-    accumulate_j(z, x, y);
+    accumulate_j(x, y, z); fixed_add4(p->i, 0, v0, v1, v2, v3); a += 4;
+    accumulate_j(y, z, x); fixed_add4(p->i, 4, v0, v1, v2, v3); a += 4;
+    accumulate_j(z, x, y); fixed_add4(p->i, 8, v0, v1, v2, v3);
 #   undef accumulate_j
 
     pm->dispx -= s_dispx; pm->dispy -= s_dispy; pm->dispz -= s_dispz;
@@ -259,9 +280,9 @@ static void advance_p_range(orc_particle_t *p0, int first, int n, orc_mover_t *p
       v2 -= v5;                                                                   \
       v3 += v5;                                                                   \
       a[offset + 0] += v0; a[offset + 1] += v1; a[offset + 2] += v2; a[offset + 3] += v3
-      ACCUMULATE_J(x, y, z, 0);
-      ACCUMULATE_J(y, z, x, 4);
-      ACCUMULATE_J(z, x, y, 8);
+      ACCUMULATE_J(x, y, z, 0); fixed_add4(ii, 0, v0, v1, v2, v3);
+      ACCUMULATE_J(y, z, x, 4); fixed_add4(ii, 4, v0, v1, v2, v3);
+      ACCUMULATE_J(z, x, y, 8); fixed_add4(ii, 8, v0, v1, v2, v3);
 #     undef ACCUMULATE_J
     } else {
       local_pm->dispx = ux; local_pm->dispy = uy; local_pm->dispz = uz;

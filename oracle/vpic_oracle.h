@@ -91,6 +91,11 @@ void orc_reduce_accumulators(orc_accumulator_t *a, const orc_grid_t *g, int n_pi
 void orc_unload_accumulator(orc_field_t *f, const orc_accumulator_t *a, const orc_grid_t *g);
 
 int  orc_move_p(orc_particle_t *p0, orc_mover_t *pm, orc_accumulator_t *a0, const orc_grid_t *g);
+/* The exact reference of the engine's deterministic accumulation.  While it is set, orc_advance_p and orc_move_p (and so
+ * orc_boundary_p_inject, orc_child_langmuir and the reflux path) add llrint((double)v * scale) of each of a streak's 12
+ * floats to a64[12 * voxel + k] (k over jx[0..3], jy[0..3], jz[0..3]) and 1 to streaks[voxel], both of orc_nv(g) voxels;
+ * the float accumulator comes out as without it.  (NULL, NULL, 0) switches it off.  Process-wide, not thread-safe. */
+void orc_set_fixed_accumulator(int64_t *a64, int32_t *streaks, double scale);
 /* n_pipeline >= 1 reproduces the reference's per-pipeline particle split, private accumulators
  * and mover segments (a0 must hold 1+n_pipeline copies); n_pipeline == 0 is the plain
  * sequential loop into one accumulator. */

@@ -3,7 +3,7 @@ rounded to 64-bit fixed point and summed as integers, so nothing that is summed 
 array, of the wavefronts or of the atomics: two runs agree BIT FOR BIT -- what the reference gets from private
 accumulators reduced in a fixed order (sf_interface/reduce_accumulators.cxx:37-55).  Per-particle results are those of
 the default mode (bit-exact against the goldens); the sums agree with the reference's float sums within the usual
-summation-order tolerance.  GPU box only."""
+summation-order tolerance.  tests/test_gpu_det_exact.py holds the same sums to an exact reference, word for word.  GPU box only."""
 import importlib
 import os
 
