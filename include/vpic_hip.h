@@ -264,6 +264,17 @@ int vpic_hip_set_push_mode(vpic_hip_engine_t *e, int mode);
  * being reordered; one that the engine would push in tile order is sorted by tile first, as before a deterministic push; any
  * other species (and every one under VPIC_HIP_MOMENTS_TILED=0) is summed with one global 64-bit atomic per contribution,
  * which is slow and correct.
+ * THE RULE of the moments, a contract (tests/test_gpu_moments_exact.py holds every word of the hydro array and of rhof to
+ * it; oracle/vpic_oracle.h, orc_set_fixed_moments, and pyorc.finalize_moments are its CPU restatement):
+ *   - each of the 8 x 14 floats c a particle adds (hydro_p.c:133-158, operation by operation, uncontracted) becomes the
+ *     integer rint(c * scale_m), to nearest even; the 14 scales are those of policy.h: moment_scales for the LARGEST |q|
+ *     that has ever gone into the species -- set, appended, injected, loaded or emitted -- also after that particle has
+ *     left (absorbed, sent away), so a species keeps its scales for the run; a species that never received a charge takes
+ *     q_ref; a selection (accumulate_hydro_p_select) takes the whole species' scales;
+ *   - accumulate_rho_p does the same with the 8 weights (rho_p.c:43-84) at the scale of the push's deposits moved by a
+ *     power of two: scale 2^-ex, 8 r8V = m 2^ex (frexp), r8V the float 1 / (8 dV);
+ *   - every call rounds each non-zero sum once, float((double)sum * (1 / scale)), and ADDS it in float to what the array
+ *     holds; a word whose sum is zero is left as it is.  So species added one after the other round once each.
  * Limits of the guarantee: rhob (the charge absorbing faces and emitters leave behind, which div-E cleaning reads) is summed
  * with float atomics in both modes; a single deposit beyond 2^14 x 4.2 q_ref (|x * scale| >= 2^51) wraps in the fixed-point
  * conversion -- give q_ref the LARGEST macro-particle charge of the run when charges differ by orders of magnitude.  The

@@ -85,7 +85,11 @@ static_assert(C_NMS + MAX_SPECIES == C_CHARGED && C_NP + MAX_SPECIES == C_NMS &&
 
 struct Species {
   float q_m = 0;
-  float q_max = 0;                   // largest |charge| of a macro-particle the host has seen go into this species (the fixed-point scale of the deterministic mode)
+  // largest |charge| of a macro-particle that has EVER gone into this species -- set, appended or injected by the host, loaded
+  // or emitted on the device (k_emit reads the largest emitted |q| back) -- also after that particle has left: the fixed-point
+  // scales of the deterministic mode follow it (tests/test_gpu_moments_exact.py: "tail_holes", test_emitted_charges_count).
+  // Not booked: arrivals from another domain (vpic_hip_exchange_inject), whose charges the host never sees.
+  float q_max = 0;
   int64_t np = 0, max_np = 0, nm = 0, max_nm = 0;
   // Dead slots among [0, np): the device-resident exchange removes a particle by marking its slot (i = -1) instead of
   // back-filling from the end of the array (boundary_p.c:264), so that the tile order survives and nothing moves under a

@@ -11,6 +11,7 @@
 // within a voxel is not the stable order of sort_p.c:67; the partition is identical).
 #include "push_device.h"
 #include <cstddef>
+#include <cstring>
 #include <algorithm>
 
 namespace vpichip {
@@ -1300,10 +1301,12 @@ int k_exchange_finish(Engine *e, const void *const *recv, int n_recv, int32_t *h
 // eps0 dY dZ dt sqrt(coef |q_m E_n^3| / dX), start on the face with a half-Maxwellian normal momentum, a Maxwellian
 // tangential one and a uniformly random age, leave their charge, negated, in rhob and become injector records
 // (record.sp_id = -1: this face does not emit).  Random numbers: the device's counter-based stream.
+// The charges are the device's own, so the largest |q| emitted comes back in *q_top (the bits of a non-negative float order
+// as unsigned integers) and k_emit books it in Species::q_max like every charge the host uploads.
 struct EmitParams { int sp_id, n_emit; float q_m, ut_perp, ut_para, coef, thresh, eps0, dt, cvac, d[3], rd[3]; unsigned seed, call; const double *draws; int draws_n; };   // draws: test mode, see vpic_hip_set_emit_draws
 __global__ __launch_bounds__(256)
 void emit_kernel(const int *__restrict__ component, int n_component, EmitParams P, const float *__restrict__ fi,
-                 float *__restrict__ rhob, GridK g, vpic_particle_injector_t *__restrict__ out) {
+                 float *__restrict__ rhob, GridK g, vpic_particle_injector_t *__restrict__ out, unsigned *__restrict__ q_top) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= n_component * P.n_emit) return;
   const int c = t / P.n_emit, id = component[c], i = id >> 5, type = id & 31;
@@ -1318,6 +1321,7 @@ void emit_kernel(const int *__restrict__ component, int n_component, EmitParams 
       const int ay = (axis + 1) % 3, az = (axis + 2) % 3;
       float qp = P.eps0 * P.d[ay] * P.d[az] * P.dt * sqrtf(P.coef * fabsf(P.q_m * en * en * en) / P.d[axis]) / (float)P.n_emit;
       if (P.q_m < 0) qp = -qp;
+      if (fabsf(qp) <= 3.4e38f) atomicMax(q_top, __float_as_uint(fabsf(qp)));          // (false for a NaN)
       float pos[3], u[3], age;
       pos[axis] = -dir;
       if (P.draws && t < P.draws_n) {
@@ -1356,16 +1360,25 @@ int k_emit(Engine *e, int sp, const int32_t *host_components, int n, int n_emit,
                   {G.dx, G.dy, G.dz}, {G.rdx, G.rdy, G.rdz}, seed, ++e->reflux_calls, e->emit_draws, (int)e->emit_draws_n};
   const size_t total = (size_t)n * n_emit;
   void *buf = nullptr;
-  VH_CHECK(hipMalloc(&buf, sizeof(int32_t) * (size_t)n + sizeof(vpic_particle_injector_t) * total + 16));
+  static_assert(sizeof(vpic_particle_injector_t) % sizeof(unsigned) == 0, "the word behind the records is aligned");
+  VH_CHECK(hipMalloc(&buf, sizeof(int32_t) * (size_t)n + sizeof(vpic_particle_injector_t) * total + 16 + sizeof(unsigned)));
   int *comp = (int *)buf;
   vpic_particle_injector_t *inj = (vpic_particle_injector_t *)((char *)buf + ((sizeof(int32_t) * (size_t)n + 15) & ~(size_t)15));
+  unsigned *q_top = (unsigned *)(inj + total), q_bits = 0;       // the largest |q| emitted (emit_kernel)
   VH_CHECK(hipMemcpyAsync(comp, host_components, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, e->stream));
+  VH_CHECK(hipMemsetAsync(q_top, 0, sizeof(unsigned), e->stream));
   hipLaunchKernelGGL(emit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, comp, n, P,
-                     reinterpret_cast<const float *>(e->fi), e->f.c[F_RHOB], e->gk, inj);
+                     reinterpret_cast<const float *>(e->fi), e->f.c[F_RHOB], e->gk, inj, q_top);
   int rc = hipGetLastError() != hipSuccess;
   if (!rc) rc = k_boundary_p_inject(e, inj, (int)total);
   (void)hipStreamSynchronize(e->stream);
+  if (!rc) rc = hipMemcpy(&q_bits, q_top, sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess;
   (void)hipFree(buf);
+  if (!rc) {
+    float q_emitted;
+    memcpy(&q_emitted, &q_bits, sizeof q_emitted);
+    e->species[sp].q_max = std::max(e->species[sp].q_max, q_emitted);
+  }
   return rc;
 }
 

@@ -360,6 +360,51 @@ def finalize(a64, scale):
     return np.ascontiguousarray(a.reshape(-1, 12)).view(L.accumulator_t).reshape(-1)
 
 
+# ---- ... and of its deterministic hydro moments and rho (csrc/moments.hip) ----
+class FixedMoments:
+    """What fixed_moments yields: the integer sums h64[nv, 14] / r64[nv], the sums of the absolute values of the same
+    integers habs64 / rabs64, the contributions per node count (hydro) / rcount (rho), skipped[2] (contributions out of
+    the fixed-point range: hydro, rho), and the scales they were taken at"""
+
+    def __init__(self, g, scales14, rho_scale):
+        nv = g.nv
+        self.scales = np.ascontiguousarray(scales14, np.float64)
+        self.rho_scale = float(rho_scale)
+        assert self.scales.shape == (14,)
+        self.h64, self.habs64 = np.zeros((nv, 14), np.int64), np.zeros((nv, 14), np.int64)
+        self.r64, self.rabs64 = np.zeros(nv, np.int64), np.zeros(nv, np.int64)
+        self.count, self.rcount = np.zeros(nv, np.int32), np.zeros(nv, np.int32)
+        self.skipped = np.zeros(2, np.int64)
+
+
+@contextlib.contextmanager
+def fixed_moments(g, scales14, rho_scale):
+    """While the block runs, accumulate_hydro_p / accumulate_rho_p also sum every contribution they add to a node as the
+    integer llrint(c * scale) -- scales14 for the 14 moments, rho_scale for the weights of rho: yields a FixedMoments;
+    the switch is cleared on the way out, always.  The float results are what they are without it."""
+    m = FixedMoments(g, scales14, rho_scale)
+    lib().orc_set_fixed_moments(_p(m.h64), _p(m.habs64), _p(m.count), _p(m.r64), _p(m.rabs64), _p(m.rcount), _p(m.skipped),
+                                _p(m.scales), C.c_double(m.rho_scale))
+    try:
+        yield m
+    finally:
+        lib().orc_set_fixed_moments(None, None, None, None, None, None, None, None, C.c_double(0.0))
+
+
+def finalize_moments(prev, sums, scales):
+    """What moments_finalize_kernel leaves in the float array `prev` (hydro_t[nv] with sums int64[nv, 14] and 14 scales, or
+    float32[nv] with sums int64[nv] and one scale): per word with a non-zero sum, prev + float32(float64(sum) * (1 / scale))
+    added in float32; a word whose sum is zero is left as it is.  Returns a new array."""
+    s = np.ascontiguousarray(sums, np.int64).reshape(len(sums), -1)
+    inv = 1.0 / np.asarray(scales, np.float64).reshape(-1)               # exact: the scales are powers of two
+    assert inv.shape == (s.shape[1],)
+    add = (s.astype(np.float64) * inv).astype(np.float32)
+    out = np.array(prev)                                                 # a contiguous copy
+    w = out.view(np.float32).reshape(len(s), -1)[:, :s.shape[1]]
+    w[...] = np.where(s != 0, w + add, w)
+    return out
+
+
 def step(f, fi, a, m, species, g, sort=False, clean_e=False, clean_b=False, sync_shared=False, det_scale=None):
     """One vpic_simulation::advance() of a single self-periodic / locally bounded domain
     (src/vpic/advance.cxx:38-214 without emitters, collisions, injection and div cleaning).

@@ -936,6 +936,42 @@ void orc_clear_rhof(orc_field_t *f, const orc_grid_t *g) {
   for (int v = 0; v < nv; v++) f[v].rhof = 0;
 }
 
+/* ------------------------------------------------------------------------------------------
+ * The exact reference of the engine's deterministic hydro moments and rho (include/vpic_hip.h: vpic_hip_set_accumulation;
+ * csrc/moments.hip: mom_add, moments_finalize_kernel -- the project's own rule, nothing of the reference's).  While the
+ * switch is on, every contribution that orc_accumulate_hydro_p / orc_accumulate_rho_p add to a node -- the float the `+=`
+ * adds, a named temporary -- is also rounded to the integer llrint((double)c * scale) (exact product: a float times a
+ * power of two; nearest-even) and summed per node and moment, with the sum of the absolute values of those integers and
+ * the number of contributions per node.  A contribution with |c * scale| >= 2^51, or a NaN, is counted in skipped[] and
+ * not added: the engine's rule.  Integer sums do not depend on the order of anything.  The float arithmetic is not
+ * touched.                                                                                                              */
+static struct {
+  int64_t *h64, *habs64, *r64, *rabs64, *skipped;
+  int32_t *hcount, *rcount;
+  double hscale[14], rscale;
+} mx;
+void orc_set_fixed_moments(int64_t *h64, int64_t *habs64, int32_t *hcount, int64_t *r64, int64_t *rabs64, int32_t *rcount,
+                           int64_t *skipped, const double *scales14, double rho_scale) {
+  mx.h64 = h64; mx.habs64 = habs64; mx.hcount = hcount; mx.r64 = r64; mx.rabs64 = rabs64; mx.rcount = rcount;
+  mx.skipped = skipped; mx.rscale = rho_scale;
+  for (int k = 0; k < 14; k++) mx.hscale[k] = scales14 ? scales14[k] : 0;
+}
+static void fixed_moment(int64_t *sum, int64_t *sum_abs, int64_t *skipped, float c, double scale) {
+  const double x = (double)c * scale;
+  if (fabs(x) < 2251799813685248.0) { const int64_t q = llrint(x); *sum += q; *sum_abs += q < 0 ? -q : q; }   /* 2^51; false for a NaN */
+  else (*skipped)++;
+}
+static void fixed_hydro_node(size_t node, const float c[14]) {
+  if (!mx.h64) return;
+  for (int k = 0; k < 14; k++) fixed_moment(&mx.h64[14 * node + k], &mx.habs64[14 * node + k], &mx.skipped[0], c[k], mx.hscale[k]);
+  mx.hcount[node]++;
+}
+static void fixed_rho_node(size_t node, float w) {
+  if (!mx.r64) return;
+  fixed_moment(&mx.r64[node], &mx.rabs64[node], &mx.skipped[1], w, mx.rscale);
+  mx.rcount[node]++;
+}
+
 /* species_advance/standard/rho_p.c:23-86 */
 void orc_accumulate_rho_p(orc_field_t *f0, const orc_particle_t *p, int n, const orc_grid_t *g) {
   const int sy = g->nx + 2, sz = sy * (g->ny + 2);
@@ -949,6 +985,11 @@ void orc_accumulate_rho_p(orc_field_t *f0, const orc_particle_t *p, int n, const
     orc_field_t *f = f0 + p->i;
     f[0].rhof += w0; f[1].rhof += w1; f[sy].rhof += w2; f[sy + 1].rhof += w3;
     f[sz].rhof += w4; f[sz + 1].rhof += w5; f[sz + sy].rhof += w6; f[sz + sy + 1].rhof += w7;
+    if (mx.r64) {                            /* (w0 .. w7 are the floats added above) */
+      const size_t v = (size_t)p->i;
+      fixed_rho_node(v, w0); fixed_rho_node(v + 1, w1); fixed_rho_node(v + sy, w2); fixed_rho_node(v + sy + 1, w3);
+      fixed_rho_node(v + sz, w4); fixed_rho_node(v + sz + 1, w5); fixed_rho_node(v + sz + sy, w6); fixed_rho_node(v + sz + sy + 1, w7);
+    }
   }
 }
 
@@ -1230,6 +1271,7 @@ void orc_accumulate_hydro_p(orc_hydro_t *h0, const orc_particle_t *p0, int n, fl
   float vx, vy, vz, ke_mc;
   float w0, w1, w2, w3, w4, w5, w6, w7;
   float qdt_2mc, qdt_4mc2, c, r8V, mc_q;
+  float m[14];
   const orc_particle_t *p;
   const orc_interpolator_t *f;
   orc_hydro_t *h;
@@ -1271,12 +1313,19 @@ void orc_accumulate_hydro_p(orc_hydro_t *h0, const orc_particle_t *p0, int n, fl
     w3  = 1+dy; w2  = w0*w3; w3 *= w1; dy  = 1-dy; w0 *= dy; w1 *= dy;
     w7  = 1+dz; w4  = w0*w7; w5  = w1*w7; w6  = w2*w7; w7 *= w3;
     dz  = 1-dz; w0 *= dz; w1 *= dz; w2 *= dz; w3 *= dz;
+    /* every contribution is a float of its own (m[]), so that the exact reference (orc_set_fixed_moments) rounds the very
+     * float the `+=` adds; the float sums are what they were */
 #   define ACCUM_HYDRO(wn)           \
-    h->jx  += wn*vx; h->jy  += wn*vy; h->jz  += wn*vz; h->rho += wn; \
+    m[0] = wn*vx; m[1] = wn*vy; m[2] = wn*vz; m[3] = wn;             \
+    h->jx  += m[0]; h->jy  += m[1]; h->jz  += m[2]; h->rho += m[3];  \
     wn *= mc_q; dx = wn*ux; dy = wn*uy; dz = wn*uz;                  \
-    h->px  += dx; h->py  += dy; h->pz  += dz; h->ke  += wn*ke_mc;    \
-    h->txx += dx*vx; h->tyy += dy*vy; h->tzz += dz*vz;               \
-    h->tyz += dy*vz; h->tzx += dz*vx; h->txy += dx*vy
+    m[4] = dx; m[5] = dy; m[6] = dz; m[7] = wn*ke_mc;                \
+    h->px  += m[4]; h->py  += m[5]; h->pz  += m[6]; h->ke  += m[7];  \
+    m[8] = dx*vx; m[9] = dy*vy; m[10] = dz*vz;                       \
+    h->txx += m[8]; h->tyy += m[9]; h->tzz += m[10];                 \
+    m[11] = dy*vz; m[12] = dz*vx; m[13] = dx*vy;                     \
+    h->tyz += m[11]; h->tzx += m[12]; h->txy += m[13];               \
+    fixed_hydro_node((size_t)(h - h0), m)
     h = h0 + ii;    ACCUM_HYDRO(w0);
     h += stride_10; ACCUM_HYDRO(w1);
     h += stride_21; ACCUM_HYDRO(w2);

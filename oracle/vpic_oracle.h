@@ -195,6 +195,15 @@ double orc_synchronize_tang_e_norm_b_self(orc_field_t *f, const orc_grid_t *g, i
 void   orc_local_adjust_rho(orc_field_t *f, const orc_grid_t *g);
 void   orc_synchronize_rho_self(orc_field_t *f, const orc_grid_t *g, int axis);
 
+/* The exact reference of the engine's deterministic hydro moments and rho.  While it is set, orc_accumulate_hydro_p adds
+ * llrint((double)c * scales14[k]) of each of the 14 floats c it adds to a node to h64[14 * node + k], the absolute value
+ * of that integer to habs64[14 * node + k] and 1 to hcount[node]; orc_accumulate_rho_p does the same with each of the 8
+ * weights at rho_scale into r64[node], rabs64[node], rcount[node] (all of orc_nv(g) nodes).  A contribution with
+ * |c * scale| >= 2^51, or a NaN, is counted in skipped[0] (hydro) / skipped[1] (rho) and not added.  The float results
+ * come out as without it.  All-NULL switches it off.  Process-wide, not thread-safe. */
+void orc_set_fixed_moments(int64_t *h64, int64_t *habs64, int32_t *hcount, int64_t *r64, int64_t *rabs64, int32_t *rcount,
+                           int64_t *skipped, const double *scales14, double rho_scale);
+
 /* Hydro moments */
 void orc_clear_hydro(orc_hydro_t *h, const orc_grid_t *g);
 void orc_accumulate_hydro_p(orc_hydro_t *h, const orc_particle_t *p, int n, float q_m,

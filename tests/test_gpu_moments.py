@@ -13,7 +13,11 @@ them in tile order); "unsorted_wants_tile" is the unsorted array under the knob,
 first.  "tile_only" (VPIC_HIP_TILE_COARSE=1) and VPIC_HIP_MOMENTS_TILED=0 run in a fresh child process each.
 "tile_tail_holes": tile order, 600 appended particles, then one step of the resident exchange with absorbing x walls which
 removes 60 particles placed for it and leaves their slots dead; its particles are not the inputs any more (the step moved
-them), so it is compared with the oracle on what get_particles returns afterwards, and bit for bit with itself."""
+them), so it is compared with the oracle on what get_particles returns afterwards, and bit for bit with itself.
+
+This file proves reproducibility (GPU results against one another) and closeness to the largest entry; correctness node by
+node -- every deterministic word against an exact reference, every float word within a derived bound, on more grids, q_m,
+charges and momenta -- is tests/test_gpu_moments_exact.py."""
 import contextlib
 import functools
 import importlib

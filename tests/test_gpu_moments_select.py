@@ -12,7 +12,10 @@ their part of what it returned.
 Float mode: within ACC_TOL = 2e-6 of each moment's largest entry in the reference.  Deterministic mode: BIT FOR BIT equal
 to accumulate_hydro_p of a second species of the same q_m that holds exactly the particles select() returns for the
 descriptor -- both calls use the fixed-point scale of |q| = 0.015, which every kept subset contains (asserted here on the
-returned particles, and on the inputs by the CPU test) -- and equal across the states that hold the same particles."""
+returned particles, and on the inputs by the CPU test) -- and equal across the states that hold the same particles.
+
+The selected moments against an exact reference, word for word (deterministic) and within a derived per-node bound (float),
+at the whole species' scale: tests/test_gpu_moments_exact.py::test_the_moments_of_a_selection."""
 import ctypes as C
 import functools
 import importlib
