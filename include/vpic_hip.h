@@ -298,6 +298,90 @@ int vpic_hip_sort_advance_p(vpic_hip_engine_t *e, int sp);
 int vpic_hip_species_sort_hint(vpic_hip_engine_t *e, int sp);          /* species_advance/standard/sort_p.c:16-102 */
 int vpic_hip_energy_p(vpic_hip_engine_t *e, int sp, double *energy); /* species_advance/standard/energy_p.cxx:124-157 (local part) */
 
+/* ---- binary Coulomb collisions of the particles of one species, or of two, cell by cell (csrc/collide.hip) ----
+ * The device counterpart of a deck's user_particle_collisions (src/vpic/advance.cxx:41-67: between the sort and the push).
+ * The reference ships the hook and no operator; this is the operator of Takizuka & Abe (J. Comput. Phys. 25, 205, 1977):
+ * the particles of a cell are paired at random and every pair is turned in its centre-of-mass frame by a random small
+ * angle.  It is NON-RELATIVISTIC in u (u is taken for the velocity in units of c: valid for |u| << 1; there is no Lorentz
+ * factor anywhere), rank-local (a cell's particles are all on this rank), and its result depends on the order of the array
+ * within a cell (the pairing is by position in the cell's range): statistically the same in any order, bit for bit only
+ * for the same array.  A relativistic (Perez-style) form is out of scope.
+ * THE RULE, a contract (tests/collide_ref.py restates it in numpy; tests/test_gpu_collide.py holds every word to it):
+ *   mix32(x):  x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16   (uint32, a bijection)
+ *   Cells are the interior voxels v = x + (nx+2) * (y + (ny+2) * z), 1 <= x <= nx ...; the particles of species s in cell v
+ *   are a contiguous range of its array (see "exact ranges" below), k = 0 .. n_s - 1 the position inside the range.
+ *   c0_s = mix32((seed ^ mix32(call * 0x9e3779b9 + s)) + mix32(rank * 0x85ebca6b + v))    (uint32 arithmetic; s the species
+ *          id, rank the grid's, v the VOXEL in either array order)
+ *   key_s(k) = mix32(c0_s + k): no two keys of a range tie.  perm_s[r] = the k whose key is the r-th smallest.
+ *   Pairs of ONE species (sp_a == sp_b), n particles in the cell, N = n:
+ *     n < 2: none.  n even: pair j = (perm[2j], perm[2j+1]), j = 0 .. n/2 - 1.
+ *     n odd: with p0, p1, p2 = perm[0], perm[1], perm[2]: pairs 0, 1, 2 = (p0,p1), (p1,p2), (p2,p0), applied in that order,
+ *       each with s2 halved; then pair 3 + m = (perm[3 + 2m], perm[4 + 2m]), m = 0 .. (n-3)/2 - 1.
+ *   Pairs of TWO species: L is the species with more particles in the cell (sp_a on a tie), S the other; n_S == 0: none.
+ *     pair j = (L[perm_L[j]], S[perm_S[j mod n_S]]), j = 0 .. n_L - 1; pairs that share their S particle are applied in
+ *     ascending j.  N = min(n_a, n_b).
+ *   The first-named particle of a pair is its FIRST particle; no particle is the first one of two pairs.
+ *   Per pair (first f, second s), IEEE float, every operation rounded once, unfused, / and sqrt correctly rounded, the
+ *   parentheses as written:
+ *     w = fabsf(q) * wq of its species (the number of physical particles a macro-particle stands for)
+ *     gx = ux_f - ux_s, gy, gz likewise;  gq = gx*gx + gy*gy;  g2 = gq + gz*gz;  gm = sqrt(g2);  gp = sqrt(gq)
+ *     gm == 0: the pair is skipped (and counted); otherwise
+ *     m_ab = (m_a * m_b) / (m_a + m_b);  V = (dx * dy) * dz of the grid
+ *     s2 = (((cvar * max(w_f, w_s)) * (float)N) * dt) / (((V * m_ab) * m_ab) * ((gm * gm) * gm));  in the triple s2 = 0.5f * s2
+ *     d = draw_N * sqrt(s2);  t = d * d
+ *     t < 2^64:  sin_t = (2 * d) / (1 + t),  omc = (2 * t) / (1 + t)      (d = tan(theta / 2); omc = 1 - cos theta)
+ *     otherwise (a NaN included):  sin_t = 0,  omc = 2
+ *     sc = sin_t * cos_phi;  ss = sin_t * sin_phi
+ *     gp != 0:  ax = gx / gp;  ay = gy / gp
+ *               Dx = ((ax * gz) * sc - (ay * gm) * ss) - gx * omc
+ *               Dy = ((ay * gz) * sc + (ax * gm) * ss) - gy * omc
+ *               Dz = (-(gp * sc)) - gz * omc
+ *     gp == 0:  Dx = gm * sc;  Dy = gm * ss;  Dz = -(gz * omc)         (gz with its sign: |g + D| = |g|)
+ *     u_f = u_f + (m_ab / m_f) * D   componentwise, done iff  w_s >= w_f || U * w_f < w_s
+ *     u_s = u_s - (m_ab / m_s) * D   componentwise, done iff  w_f >= w_s || U * w_s < w_f
+ *   so that a light macro-particle is always turned and a heavy one with probability w_light / w_heavy (momentum and
+ *   energy are then conserved on average only; with equal weights exactly, up to rounding).
+ *   Draws: four numbers per pair, (draw_N, cos_phi, sin_phi, U).  Normally from the counter stream of the pair: with c0 of
+ *   the first particle's species and j the pair's number above, r_i = mix32(mix32(c0 ^ 0x2545f491) + 4 j + i), i = 0 .. 3,
+ *   unit(r) = ((float)(r >> 8) + 0.5f) / 2^24: draw_N = sqrt(-2 log unit(r_0)) cos(2 pi unit(r_1)), phi = 2 pi unit(r_2),
+ *   U = unit(r_3) -- the device's own log, cos and sin: statistically specified, not bit for bit.  Same array, seed and
+ *   call: same result.  With vpic_hip_set_collide_draws (parity tests) they are read from draws[4 i .. 4 i + 3], i the first
+ *   particle's index in its species' array; the table must cover the longer of the two arrays.
+ * cvar = (q_a q_b)^2 ln(Lambda) / (8 pi eps0^2 c^3) in the deck's units, q and m those of a PHYSICAL particle; dt the time
+ * this call stands for (the collision interval times the grid's dt).
+ * What the call touches: ux, uy, uz of the two species and nothing else -- positions, voxels, charges, tags, the order of the
+ * arrays, partition[] / tpart[], the push's pending histogram and windows stay as they are; host mirrors go stale as after a
+ * push.  Exact ranges: a species sorted by voxel with partition[] valid, or in tile order by cell with nothing appended and
+ * no dead slots, is collided where it lies when a checking pass (4 B per particle) finds every particle inside the range of
+ * its own voxel; any other (never sorted, sorted by tile only, appended to, with dead slots, pushed since the sort so that a
+ * particle left its cell, a sort pending inside the next push) is SORTED FIRST, in the order the engine would sort it into
+ * now and never by tile only; a pending sort inside the push is carried out as a plain sort.  A cell that holds more than
+ * VPIC_HIP_COLLIDE_MAX_CELL particles of one species makes the call fail before any momentum is written (a sort it needed
+ * has then happened).  Two kernel instances, chosen from the fullest cell: a wavefront per cell while both species have at
+ * most 64 there, a workgroup per cell (the cell's momenta, weights and keys in LDS) above.
+ * Fails (non-zero, vpic_hip_last_error names the argument) on a NULL c, an unknown sp_a / sp_b, m_a / m_b / wq_a / wq_b not
+ * above 0, cvar or dt negative (or NaN), a draws table shorter than an array; nothing is touched then. */
+typedef struct { int sp_a, sp_b;            /* sp_a == sp_b: collisions within one species (m_b, wq_b are then not read) */
+                 float m_a, m_b;            /* mass of a physical particle of each species */
+                 float wq_a, wq_b;          /* weight of a macro-particle = |q| * wq  (wq = 1 / |charge of a physical particle|) */
+                 float cvar;                /* (q_a q_b)^2 ln(Lambda) / (8 pi eps0^2 c^3) in the deck's units */
+                 float dt;                  /* the time this call stands for (interval * grid dt) */
+                 uint32_t seed, call; } vpic_hip_collision_t;
+VPIC_HIP_STATIC_ASSERT(sizeof(vpic_hip_collision_t) == 40, "vpic_hip_collision_t layout");
+#define VPIC_HIP_COLLIDE_MAX_CELL 1024       /* particles of ONE species in one cell: 6 LDS words each, 48 KB for two species at the cap */
+int vpic_hip_collide(vpic_hip_engine_t *e, const vpic_hip_collision_t *c);
+/* The last call: out[0] cells with a pair, out[1] pairs scattered, out[2] pairs skipped (gm == 0), out[3] pairs of which only
+ * one particle (or neither) was updated (weights), out[4] the fullest cell (particles of one species), out[5] 1 if the call
+ * sorted a species first. */
+int vpic_hip_collide_stats(vpic_hip_engine_t *e, int64_t out[6]);
+/* ... and the kernel instance its launch was: 1 a wavefront per cell, 2 a workgroup per cell, 0 none (nothing to collide, or
+ * the call failed before its launch).  VPIC_HIP_COLLIDE_INSTANCE=group (read when the engine is created; tests) takes the
+ * workgroup instance for every launch; =wave is the default choice and cannot be forced on a cell of more than 64. */
+int vpic_hip_collide_instance(vpic_hip_engine_t *e, int *instance);
+/* parity tests: the four draws of every pair from a table in host memory, 4 floats per particle index (see above); n = 0
+ * switches back to the counter stream */
+int vpic_hip_set_collide_draws(vpic_hip_engine_t *e, const float *draws, int64_t n);
+
 /* ---- energy spectra of a species (the diagnostic of decks/trecon-part/energy.cxx, computed where the particles are) ----
  * One pass over the species' stored momenta (no half-step field correction, unlike energy_p).  Per live particle
  * (dead slots are skipped, particles appended since the last sort are included), energy.cxx:96-108 restated:

@@ -109,6 +109,11 @@ def lib():
     L.vpic_hip_species_select.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 4
     L.vpic_hip_species_select_stats.argtypes = [C.c_void_p, C.c_void_p]
     L.vpic_hip_accumulate_hydro_p_select.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(L, "vpic_hip_collide"):                      # (an older build of the ABI under VPIC_HIP_LIB has no collisions)
+        L.vpic_hip_collide.argtypes = [C.c_void_p, C.c_void_p]
+        L.vpic_hip_collide_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.vpic_hip_collide_instance.argtypes = [C.c_void_p, C.c_void_p]
+        L.vpic_hip_set_collide_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     L.vpic_hip_dump_gather.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_size_t]
     _lib = L
     return L
@@ -131,4 +136,5 @@ vpic_hip_species_distribution vpic_hip_species_distribution_stats vpic_hip_momen
 vpic_hip_species_distribution_sums vpic_hip_species_distribution_sums_stats
 vpic_hip_cell_distribution vpic_hip_cell_distribution_stats
 vpic_hip_species_select_count vpic_hip_species_select vpic_hip_species_select_stats
-vpic_hip_accumulate_hydro_p_select""".split()
+vpic_hip_accumulate_hydro_p_select
+vpic_hip_collide vpic_hip_collide_stats vpic_hip_collide_instance vpic_hip_set_collide_draws""".split()

@@ -258,6 +258,7 @@ struct Knobs {
   int unload_tiled = 1;            // VPIC_HIP_UNLOAD_TILED: clear_jf + unload_accumulator 0 one thread per voxel through L1 / L2 (rounds 2-3), 2 through LDS tiles, 1 (default) tiles on grids large enough to fill the chip with them
   int field_tiles = 0;             // VPIC_HIP_FIELD_TILES: advance_b / advance_e (one material) 0 (default) one thread per voxel through L1 / L2, 2 through LDS tiles, 1 tiles on grids large enough to fill the chip with them -- measured TWICE as slow (fields.hip)
   bool rho_per_particle = false, hydro_per_particle = false;   // VPIC_HIP_RHO_PER_PARTICLE, VPIC_HIP_HYDRO_PER_PARTICLE
+  bool collide_group = false;      // VPIC_HIP_COLLIDE_INSTANCE=group: vpic_hip_collide launches the workgroup-per-cell instance whatever the fullest cell (tests)
   bool moments_tiled = true;       // VPIC_HIP_MOMENTS_TILED=0: accumulate_hydro_p / accumulate_rho_p never sum by tile (policy.h: plan_moments; A/B timing)
 };
 Knobs read_knobs();
@@ -387,6 +388,13 @@ struct Engine {
   vpic_particle_t *sel_p = nullptr; float *sel_f = nullptr; int64_t *sel_i = nullptr; size_t sel_p_n = 0, sel_f_n = 0, sel_i_n = 0;
   DiagStats sel_stats;
 
+  // binary collisions (collide.hip), allocated by the first call: the test mode's draws (4 floats per particle index), the
+  // words its kernels write on the device and the pinned words they come back through (COLLIDE_WORDS), what the last call
+  // left (vpic_hip_collide_stats) and the instance it launched (policy.h: CollideInstance as 0 / 1 / 2)
+  float *collide_draws = nullptr; int64_t collide_draws_n = 0;
+  unsigned long long *collide_dev = nullptr, *collide_host = nullptr;
+  int64_t collide_last[6] = {0, 0, 0, 0, 0, 0}; int collide_instance = 0;
+
   hipEvent_t step_done[4] = {}; int64_t steps_enqueued = 0;   // vpic_hip_step: the host stays at most two steps ahead of the device
   // profiling
   bool profile = false;
@@ -484,6 +492,8 @@ constexpr int CELL_DIST_STATS = 8;       // words of Engine::cell_stats
 int k_cell_distribution(Engine *e, const vpic_hip_dist_t &d, const vpic_hip_dist_value_t *v, int n_val);   // cell_dist.hip: into Engine::cell_counts / cell_host, cell_sums / cell_sums_host; waits for the stream
 // select.hip: launches 1 and 2 (count_only: no masks), and launch 3 into Engine::sel_p / sel_f / sel_i where asked for; waits for the stream
 int k_species_select(Engine *e, Species &s, const vpic_hip_select_t &d, int64_t cap, bool want_p, bool want_f, bool want_i, bool count_only);
+// collide.hip: the checking pass, the sorts it asks for, the launch; wants_tile_a / _b: the order a sort of that species would produce now
+int k_collide(Engine *e, const vpic_hip_collision_t &c, bool wants_tile_a, bool wants_tile_b);
 int k_sort_p(Engine *e, Species &s, bool tile_order = false, bool may_fuse = false);   // may_fuse: the caller pushes the species next (see Species::fuse_pending)
 int k_sort_scan(Engine *e, const int *counts, int *starts, int n1);                  // exclusive scan of counts[0..n1) into starts[] and Engine::sort_next[]
 int k_sort_check(Engine *e, Species &s, const int *starts, int n1);                    // every cursor ended where the next key begins? (PW_SORT_CHECK; the next push fails loudly otherwise)

@@ -51,6 +51,7 @@ Knobs read_knobs() {
   k.rho_per_particle = getenv("VPIC_HIP_RHO_PER_PARTICLE") != nullptr;
   k.hydro_per_particle = getenv("VPIC_HIP_HYDRO_PER_PARTICLE") != nullptr;
   if (const char *v = getenv("VPIC_HIP_MOMENTS_TILED")) k.moments_tiled = atoi(v) != 0;
+  if (const char *v = getenv("VPIC_HIP_COLLIDE_INSTANCE")) k.collide_group = v[0] == 'g';
   return k;
 }
 
@@ -187,6 +188,7 @@ static void destroy(Engine *e) {
   (void)hipFree(e->face_buf[0]); (void)hipFree(e->face_buf[1]);
   for (int f = 0; f < 6; f++) (void)hipFree(e->send_buf[f]);
   (void)hipFree(e->local_buf); (void)hipFree(e->reflux_draws); (void)hipFree(e->emit_draws);
+  (void)hipFree(e->collide_draws); (void)hipFree(e->collide_dev); (void)hipHostFree(e->collide_host);
   (void)hipFree(e->hole_list); (void)hipFree(e->fill_list); (void)hipFree(e->tail_flag);
   (void)hipFree(e->sp_table_dev); (void)hipHostFree(e->sp_table_host); (void)hipFree(e->xmsg_dev); (void)hipHostFree(e->xmsg_host);
   (void)hipFree(e->retry_buf); (void)hipFree(e->tile_list[0]); (void)hipFree(e->tile_list[1]);
@@ -515,6 +517,17 @@ int vpic_hip_debug_set_particles_any_voxel(vpic_hip_engine_t *e, int sp, const v
   host_will_read(p, sizeof(*p) * (size_t)np);
   return k_particles_from_aos(e, e->species[sp], p, np, 0, true);
 }
+// test hook (not part of include/vpic_hip.h): overwrite ux, uy, uz of the species' array slots [0, n), n its extent, and NOTHING else --
+// not the order, not the bookkeeping.  The sorts place the particles of a cell in no fixed order, so a test that wants to run
+// vpic_hip_collide twice on the same array (tests/test_gpu_collide.py: test_seeds) puts the momenta back instead of uploading again.
+int vpic_hip_debug_set_momenta(vpic_hip_engine_t *e, int sp, const float *ux, const float *uy, const float *uz, int64_t n) {
+  ENGINE(e); SPECIES(e, sp);
+  Species &s = e->species[sp];
+  if (!ux || !uy || !uz || n != s.np) VH_FAIL("Bad momenta: %lld, the species' extent is %lld", (long long)n, (long long)s.np);
+  if (n == 0) return 0;
+  if (copy_in(e, s.p.ux, ux, sizeof(float) * (size_t)n) || copy_in(e, s.p.uy, uy, sizeof(float) * (size_t)n)) return 1;
+  return copy_in(e, s.p.uz, uz, sizeof(float) * (size_t)n);
+}
 int vpic_hip_species_get_tile_partition(vpic_hip_engine_t *e, int sp, int32_t *tpart, int64_t *count) {
   ENGINE(e); SPECIES(e, sp);
   Species &s = e->species[sp];
@@ -663,6 +676,44 @@ int vpic_hip_energy_p(vpic_hip_engine_t *e, int sp, double *energy) {
   ENGINE(e); SPECIES(e, sp);
   if (!energy) VH_FAIL("Bad energy");
   return k_energy_p(e, e->species[sp], energy);
+}
+// Binary collisions (collide.hip).  The arguments are checked here, before anything is touched; the message names the argument.
+int vpic_hip_collide(vpic_hip_engine_t *e, const vpic_hip_collision_t *c) {
+  ENGINE(e);
+  if (!c) VH_FAIL("collide: NULL c");
+  if (c->sp_a < 0 || (size_t)c->sp_a >= e->species.size()) VH_FAIL("collide: sp_a = %d is not a species", c->sp_a);
+  if (c->sp_b < 0 || (size_t)c->sp_b >= e->species.size()) VH_FAIL("collide: sp_b = %d is not a species", c->sp_b);
+  const bool same = c->sp_a == c->sp_b;
+  if (!(c->m_a > 0)) VH_FAIL("collide: m_a = %g must be above 0", (double)c->m_a);
+  if (!(c->wq_a > 0)) VH_FAIL("collide: wq_a = %g must be above 0", (double)c->wq_a);
+  if (!same && !(c->m_b > 0)) VH_FAIL("collide: m_b = %g must be above 0", (double)c->m_b);
+  if (!same && !(c->wq_b > 0)) VH_FAIL("collide: wq_b = %g must be above 0", (double)c->wq_b);
+  if (!(c->cvar >= 0)) VH_FAIL("collide: cvar = %g must not be negative", (double)c->cvar);
+  if (!(c->dt >= 0)) VH_FAIL("collide: dt = %g must not be negative", (double)c->dt);
+  const int64_t longest = std::max(e->species[c->sp_a].np, e->species[c->sp_b].np);
+  if (e->collide_draws_n > 0 && e->collide_draws_n < longest)
+    VH_FAIL("collide: the draws table holds %lld particles, the longer array %lld", (long long)e->collide_draws_n, (long long)longest);
+  return k_collide(e, *c, wants_tile_order(e, e->species[c->sp_a]), wants_tile_order(e, e->species[c->sp_b]));
+}
+int vpic_hip_collide_stats(vpic_hip_engine_t *e, int64_t out[6]) {
+  ENGINE(e); if (!out) VH_FAIL("Bad output array");
+  for (int k = 0; k < 6; k++) out[k] = e->collide_last[k];
+  return 0;
+}
+int vpic_hip_collide_instance(vpic_hip_engine_t *e, int *instance) {
+  ENGINE(e); if (!instance) VH_FAIL("Bad output");
+  *instance = e->collide_instance;
+  return 0;
+}
+int vpic_hip_set_collide_draws(vpic_hip_engine_t *e, const float *draws, int64_t n) {
+  ENGINE(e);
+  if (n < 0 || (n > 0 && !draws) || n > (1ll << 28)) VH_FAIL("Bad draw table");
+  if (e->collide_draws) { (void)hipFree(e->collide_draws); e->collide_draws = nullptr; }
+  e->collide_draws_n = 0;
+  if (n == 0) return 0;
+  VH_CHECK(hipMalloc(&e->collide_draws, sizeof(float) * 4 * (size_t)n));
+  e->collide_draws_n = n;
+  return copy_in(e, e->collide_draws, draws, sizeof(float) * 4 * (size_t)n);
 }
 // the ranges of a distribution or a selection (`what` names the caller in the message)
 static int check_range_count(const char *what, int n_sel) {

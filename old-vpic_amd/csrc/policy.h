@@ -1,6 +1,6 @@
 // policy.h -- the engine's host decisions over plain values: the sort and the push (vpic_hip_step, sort_p, advance_p), whose
-// callers read their HIP events and pinned words once and hand in what they read, the moments, and the launch shapes of the
-// passes over one species (spectrum.hip, distribution.hip).  Plain C++17, no HIP: tests/policy_check.cpp builds it with the
+// callers read their HIP events and pinned words once and hand in what they read, the moments, the collisions (collide.hip),
+// and the launch shapes of the passes over one species (spectrum.hip, distribution.hip).  Plain C++17, no HIP: tests/policy_check.cpp builds it with the
 // host compiler alone.
 #pragma once
 #include <stdint.h>
@@ -427,6 +427,38 @@ inline MomentPlan plan_moments(const MomentInputs &in) {
 inline MomentPlan plan_moments_select(const MomentInputs &in) {
   MomentPlan pl;
   pl.path = in.tiled_knob && in.tile_valid && in.tpart_ok && in.nm == 0 ? MomentPath::tiled : MomentPath::per_particle;
+  return pl;
+}
+
+// vpic_hip_collide (collide.hip): where the two species are collided and by which kernel instance.
+// A species has EXACT cell ranges when it is sorted by voxel with partition[] valid, or in tile order by cell (not by tile only)
+// with nothing appended (n_sorted == np), no dead slots, no sort pending inside its next push -- and the checking pass, once
+// it has run, found every particle inside the range of its own voxel (check_failed: it ran and did not; a push since the
+// sort that moved a particle out of its cell shows there).  Such a species is collided where it lies; any other is sorted
+// first (in the order the engine would sort it into now, never by tile only: the caller's business) and checked again.
+// fullest: particles of this species in its fullest cell, as the checking pass counted them (0 before it has run).
+struct CollideSpecies {
+  bool partition_valid = false, tile_valid = false, coarse_sorted = false, fuse_pending = false, check_failed = false;
+  int64_t np = 0, n_sorted = 0, n_holes = 0, fullest = 0;
+};
+enum class CollideInstance { none, wave, group };   // a wavefront per cell (both species at most COLLIDE_WAVE_CELL there), a workgroup per cell
+constexpr int COLLIDE_WAVE_CELL = 64;
+struct CollidePlan { bool sort_a = false, sort_b = false, over_cap = false; CollideInstance instance = CollideInstance::none; };
+inline bool collide_ranges_exact(const CollideSpecies &s) {
+  if (s.np == 0) return true;                                                  // nothing to pair: no range is read
+  if (s.check_failed || s.n_holes > 0 || s.fuse_pending) return false;
+  if (s.tile_valid) return !s.coarse_sorted && s.n_sorted == s.np;
+  return s.partition_valid;
+}
+// same: sp_a == sp_b (b is then not looked at); cap: VPIC_HIP_COLLIDE_MAX_CELL; force_group: VPIC_HIP_COLLIDE_INSTANCE=group
+inline CollidePlan plan_collide(const CollideSpecies &a, const CollideSpecies &b, bool same, int cap, bool force_group) {
+  CollidePlan pl;
+  pl.sort_a = !collide_ranges_exact(a);
+  pl.sort_b = !same && !collide_ranges_exact(b);
+  const int64_t fullest = same ? a.fullest : std::max(a.fullest, b.fullest);
+  pl.over_cap = fullest > cap;
+  if (pl.sort_a || pl.sort_b || pl.over_cap || fullest == 0) return pl;        // (nothing is launched before the ranges are exact)
+  pl.instance = fullest <= COLLIDE_WAVE_CELL && !force_group ? CollideInstance::wave : CollideInstance::group;
   return pl;
 }
 

@@ -121,6 +121,13 @@ class SelectDesc(C.Structure):
 
 
 assert C.sizeof(SelectDesc) == 136
+class CollisionDesc(C.Structure):
+    """vpic_hip_collision_t (include/vpic_hip.h)"""
+    _fields_ = [("sp_a", C.c_int), ("sp_b", C.c_int), ("m_a", C.c_float), ("m_b", C.c_float), ("wq_a", C.c_float), ("wq_b", C.c_float),
+                ("cvar", C.c_float), ("dt", C.c_float), ("seed", C.c_uint32), ("call", C.c_uint32)]
+
+
+assert C.sizeof(CollisionDesc) == 40
 SELECT_TAG_RANGE, SELECT_TAG_EVERY = 1, 2                                                      # VPIC_HIP_SELECT_*
 SelectResult = collections.namedtuple("SelectResult", "count particles fields index")
 
@@ -456,6 +463,43 @@ class Engine:
         e = C.c_double()
         self._ck(self._l.vpic_hip_energy_p(self._h, sp, C.byref(e)))
         return e.value
+
+    # ---- binary Coulomb collisions (include/vpic_hip.h: vpic_hip_collide) ----
+    def collide(self, sp_a, sp_b=None, *, m_a, m_b=None, wq_a, wq_b=None, cvar, dt, seed, call):
+        """Takizuka-Abe collisions of the particles of species sp_a among themselves (sp_b None or sp_a) or with those of
+        sp_b, cell by cell on the device; only ux, uy, uz of the two species change.  m: mass of a physical particle, wq:
+        1 / |charge of a physical particle| (a macro-particle weighs |q| * wq), cvar = (q_a q_b)^2 ln(Lambda) / (8 pi eps0^2
+        c^3), dt the time the call stands for, (seed, call) the counter of its random stream.  Non-relativistic (|u| << 1),
+        rank-local, at most COLLIDE_MAX_CELL particles of a species per cell; a species whose cell ranges are not exact is
+        sorted first (collide_stats()["sorted_first"]).  A copy of the species' particles held on the host is stale afterwards."""
+        if sp_b is None:
+            sp_b = sp_a
+        same = int(sp_b) == int(sp_a)
+        d = CollisionDesc(int(sp_a), int(sp_b), float(m_a), float(m_a if m_b is None and same else m_b if m_b is not None else -1.0),
+                          float(wq_a), float(wq_a if wq_b is None and same else wq_b if wq_b is not None else -1.0),
+                          float(cvar), float(dt), int(seed) & 0xffffffff, int(call) & 0xffffffff)
+        self._ck(self._l.vpic_hip_collide(self._h, C.byref(d)))
+
+    def collide_stats(self):
+        """dict of the last collide call: cells with a pair, pairs scattered, pairs skipped (no relative velocity), pairs
+        of which not both particles were updated (unequal weights), the fullest cell (particles of one species), whether a
+        species was sorted first, and the kernel instance that ran ("wave", "group" or None)."""
+        out = (C.c_int64 * 6)()
+        self._ck(self._l.vpic_hip_collide_stats(self._h, out))
+        inst = C.c_int(0)
+        self._ck(self._l.vpic_hip_collide_instance(self._h, C.byref(inst)))
+        d = dict(zip(("cells", "pairs", "skipped", "one_sided", "fullest_cell", "sorted_first"), [int(v) for v in out]))
+        d["instance"] = (None, "wave", "group")[inst.value]
+        return d
+
+    def set_collide_draws(self, draws):
+        """Test mode of collide(): draws[i] = (normal, cos phi, sin phi, uniform) for the pair whose first particle is at index
+        i of its species' array, float32[n, 4]; None switches back to the device's counter stream."""
+        if draws is None:
+            self._ck(self._l.vpic_hip_set_collide_draws(self._h, None, 0))
+            return
+        d = np.ascontiguousarray(draws, np.float32).reshape(-1, 4)
+        self._ck(self._l.vpic_hip_set_collide_draws(self._h, d.ctypes.data_as(C.c_void_p), len(d)))
 
     # ---- energy spectra (include/vpic_hip.h: vpic_hip_energy_spectrum) ----
     def energy_spectrum(self, sp, n_lin=0, d_lin=0.0, n_log=0, log_lo=0.0, d_log=0.0):

@@ -598,6 +598,27 @@ void vpic_simulation::energy_spectrum(species_t *sp, int nex, double dke, float 
     for (int k = 0; k < nbin; k++) spectrum[k] = (float)counts[k];
   }
 }
+void vpic_simulation::collide(species_t *a, species_t *b, const collide_params_t &prm) {
+  if (!a) ERROR(("Invalid species"));
+  if (!b) b = a;
+  const int ia = resident_id(a->p), ib = resident_id(b->p);
+  if (!engine || ia < 0 || ib < 0) ERROR(("collide before the run has started is not supported by this host"));
+  if (prm.interval < 1) ERROR(("collide: interval %d", prm.interval));
+  if (step % prm.interval) return;
+  mirrors_after_user_code();                              // what the hook wrote so far goes to the device; the mirrors are stale from here
+  vpic_hip_collision_t c;
+  memset(&c, 0, sizeof(c));
+  c.sp_a = ia; c.sp_b = ib;
+  c.m_a = (float)prm.m_a; c.m_b = (float)(a == b ? prm.m_a : prm.m_b);
+  c.wq_a = (float)(1.0 / fabs(prm.q_a)); c.wq_b = (float)(1.0 / fabs(a == b ? prm.q_a : prm.q_b));
+  c.cvar = (float)prm.cvar; c.dt = (float)((double)prm.interval * (double)grid->dt);
+  c.seed = prm.seed; c.call = (uint32_t)step;
+  CK(vpic_hip_collide(engine, &c));
+  // both species lie sorted by cell now (they did, or the call sorted them): a sort that was due this step has been made
+  if ((size_t)ia < sort_pending.size()) sort_pending[(size_t)ia] = 0;
+  if ((size_t)ib < sort_pending.size()) sort_pending[(size_t)ib] = 0;
+  mirrors_stale();
+}
 // a deck's histogram for the engine: position axes and ranges from physical units to cells of this domain; x_code: the
 // code of X, with Y and Z behind it (a particle's VPIC_HIP_COORD_X, or a cell's VPIC_HIP_CELL_X)
 static vpic_hip_dist_t distribution_in_cells(const vpic_hip_dist_t &d, const grid_t *grid, int x_code = VPIC_HIP_COORD_X) {

@@ -46,6 +46,8 @@ assert material_coefficient_t.itemsize == 64
 # boundary codes (src/grid/grid.h:68-69).
 PEC_FIELDS, SYMMETRIC_FIELDS, PMC_FIELDS, ABSORB_FIELDS = -1, -2, -3, -4
 REFLECT_PARTICLES, ABSORB_PARTICLES = -1, -2
+# most particles of ONE species in one cell that Engine.collide takes (VPIC_HIP_COLLIDE_MAX_CELL, include/vpic_hip.h)
+COLLIDE_MAX_CELL = 1024
 
 
 def nv(nx, ny, nz):
