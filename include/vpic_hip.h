@@ -242,8 +242,10 @@ int vpic_hip_set_push_mode(vpic_hip_engine_t *e, int mode);
  * every instance of advance_p and on the injection path; oracle/vpic_oracle.h, orc_set_fixed_accumulator, and pyorc.fixed_scale
  * / finalize are its CPU restatement, pinned on the compiled reference by tests/test_det_ref.py):
  *   - the scale is the power of two  scale = 2^(37 - ex),  4.2 q = m 2^ex with 0.5 <= m < 1 (frexp),  where q is q_ref when
- *     q_ref > 0 and otherwise the largest |q| the host has put into any species so far (set / appended / injected particles) at
- *     the moment the first deterministic kernel after this call adds; it then stays until the next vpic_hip_set_accumulation;
+ *     q_ref > 0 and otherwise the largest |q| that has gone into any species so far (set / appended / injected particles, and
+ *     arrivals from other domains once _exchange_finish has booked them) at the moment the first deterministic kernel after this
+ *     call adds; it then stays until the next vpic_hip_set_accumulation.  A domain that knows no charge at all when the first
+ *     message arrives takes the largest finite |q| of that message's records (one extra read-back, once);
  *   - each of the 12 floats v of each straight streak -- formed operation by operation as the reference's scalar code forms them
  *     (advance_p.cxx:131-162 for a particle that stays in its cell, move_p.c:76-100 for every segment of one that does not,
  *     its v5 with the last multiply in double), uncontracted, in either push mode -- becomes the integer rint(v * scale),
@@ -268,8 +270,9 @@ int vpic_hip_set_push_mode(vpic_hip_engine_t *e, int mode);
  * it; oracle/vpic_oracle.h, orc_set_fixed_moments, and pyorc.finalize_moments are its CPU restatement):
  *   - each of the 8 x 14 floats c a particle adds (hydro_p.c:133-158, operation by operation, uncontracted) becomes the
  *     integer rint(c * scale_m), to nearest even; the 14 scales are those of policy.h: moment_scales for the LARGEST |q|
- *     that has ever gone into the species -- set, appended, injected, loaded or emitted -- also after that particle has
- *     left (absorbed, sent away), so a species keeps its scales for the run; a species that never received a charge takes
+ *     that has ever gone into the species -- set, appended, injected, loaded, emitted, or ARRIVED from another domain
+ *     (_exchange_inject, booked by _exchange_finish; _boundary_p_inject: tests/test_gpu_exchange.py) -- also after that
+ *     particle has left (absorbed, sent away), so a species keeps its scales for the run; a species that never received a charge takes
  *     q_ref; a selection (accumulate_hydro_p_select) takes the whole species' scales;
  *   - accumulate_rho_p does the same with the 8 weights (rho_p.c:43-84) at the scale of the push's deposits moved by a
  *     power of two: scale 2^-ex, 8 r8V = m 2^ex (frexp), r8V the float 1 / (8 dV);
@@ -722,12 +725,15 @@ int vpic_hip_advance_p_async(vpic_hip_engine_t *e, int sp);
  * in tile order is pushed whole by phase 1 (phase 2 then does nothing).  phase 0 = _advance_p_async. */
 int vpic_hip_advance_p_phase(vpic_hip_engine_t *e, int sp, int phase);
 /* _exchange_pack for the species whose bit is set in species_mask only (messages per species: species k is on the wire
- * while species k+1 is pushed).  A shared face given no message (null / capacity 0) is closed for the round. */
+ * while species k+1 is pushed).  A shared face given no message (null / capacity 0) is closed for the round: the movers
+ * bound for it stay alive and parked (flag 2, _species_nm > 0 after _finish), the other faces are served as usual, and a
+ * message the face is given in a later round -- of the same _exchange_begin ... _exchange_finish or of the next -- is
+ * filled from its first slot, with a header that counts that round's movers only. */
 int vpic_hip_exchange_pack_species(vpic_hip_engine_t *e, uint32_t species_mask, void *const dev_msg[6], const int32_t cap[6], int mover_cap);
 int vpic_hip_exchange_begin(vpic_hip_engine_t *e);
 int vpic_hip_exchange_pack(vpic_hip_engine_t *e, void *const dev_msg[6], const int32_t cap[6], int mover_cap);
 int vpic_hip_exchange_inject(vpic_hip_engine_t *e, const void *dev_msg, int cap);
-int vpic_hip_exchange_finish(vpic_hip_engine_t *e, const void *const *dev_msgs, int n_msgs /* <= 64: 3 rounds x 6 faces x sent and received, and spare */, int32_t *headers /* 4 per message */, int32_t *flags);
+int vpic_hip_exchange_finish(vpic_hip_engine_t *e, const void *const *dev_msgs, int n_msgs /* <= 192 (more is an argument error): per-species rounds and recovery rounds x 6 faces x sent and received, and spare */, int32_t *headers /* 4 per message */, int32_t *flags);
 int vpic_hip_boundary_p_counts(vpic_hip_engine_t *e, int32_t ns[6]);
 void *vpic_hip_boundary_p_send_buffer(vpic_hip_engine_t *e, int face);          /* device vpic_particle_injector_t[] */
 /* copy the injectors waiting on `face` (counts from _counts) into a device buffer of the caller */

@@ -73,22 +73,24 @@ inline void magic_div(unsigned d, unsigned &mul, unsigned &shift) {
 // device counters (ints, Engine::counters): [0] movers of a species beyond MAX_SPECIES (drop-in twins), [8..13]
 // injectors per face, [14] holes, [15] fills, [16+s] np of species s while particles are exchanged, [48+s] movers of
 // species s (written by advance_p and by the injection), [80] species that received charge, [81] overflow flags,
-// [82] movers parked because their message was full, [96+s] dead slots of species s (removals of the resident exchange)
-enum { C_NM = 0, C_DISORDER = 1, C_LOCAL = 2, C_SEND = 8, C_HOLES = 14, C_FILLS = 15, C_NP = 16, C_NMS = 48, C_CHARGED = 80, C_OVER = 81, C_RETRY = 82, C_NHOLE = 96, C_TOTAL = 128 };
+// [82] movers parked because their message was full, [83] the largest |q| of a message looked at ahead of its injection, [96+s] dead slots of species s (removals of the resident exchange),
+// [128+s] the largest finite |q| an injection appended to species s, as the bits of that float (boundary_inject_kernel)
+enum { C_NM = 0, C_DISORDER = 1, C_LOCAL = 2, C_SEND = 8, C_HOLES = 14, C_FILLS = 15, C_NP = 16, C_NMS = 48, C_CHARGED = 80, C_OVER = 81, C_RETRY = 82, C_QMSG = 83, C_NHOLE = 96, C_QTOP = 128, C_TOTAL = 160 };
 constexpr int MAX_SPECIES = 32;
 constexpr int HEADER_BASE = 256, MAX_HEADERS = 192;   // Engine::host_counters: [0, C_TOTAL) the counters, [HEADER_BASE, + 4 x MAX_HEADERS) message headers
 constexpr int RETRY_CAP = 1 << 16;                     // movers a step may park because a message was full (vpic_hip_exchange_*)
 // C_OVER bits: 1 more movers than a round's kernels were launched for (the rest waits for the next round), 2 a message was
 // full (the movers are parked and offered again), 4 a species ran out of particle slots, 8 of mover slots, 16 more
 // parked movers than RETRY_CAP (4, 8, 16: particles were lost)
-static_assert(C_NMS + MAX_SPECIES == C_CHARGED && C_NP + MAX_SPECIES == C_NMS && C_NHOLE + MAX_SPECIES == C_TOTAL, "counter layout");     // species tables handed to kernels by value (boundary_p), per-species host slots
+static_assert(C_NMS + MAX_SPECIES == C_CHARGED && C_NP + MAX_SPECIES == C_NMS && C_NHOLE + MAX_SPECIES == C_QTOP && C_QTOP + MAX_SPECIES == C_TOTAL && C_TOTAL <= HEADER_BASE, "counter layout");     // species tables handed to kernels by value (boundary_p), per-species host slots
 
 struct Species {
   float q_m = 0;
   // largest |charge| of a macro-particle that has EVER gone into this species -- set, appended or injected by the host, loaded
   // or emitted on the device (k_emit reads the largest emitted |q| back) -- also after that particle has left: the fixed-point
   // scales of the deterministic mode follow it (tests/test_gpu_moments_exact.py: "tail_holes", test_emitted_charges_count).
-  // Not booked: arrivals from another domain (vpic_hip_exchange_inject), whose charges the host never sees.
+  // Arrivals from another domain count too: the injection kernel keeps the largest |q| it appended per species in a counter
+  // word (C_QTOP) and k_exchange_finish / k_boundary_p_inject book it (tests/test_gpu_exchange.py: charge bookkeeping).
   float q_max = 0;
   int64_t np = 0, max_np = 0, nm = 0, max_nm = 0;
   // Dead slots among [0, np): the device-resident exchange removes a particle by marking its slot (i = -1) instead of
@@ -409,7 +411,8 @@ struct Engine {
 };
 
 int ensure_stage(Engine *e, size_t bytes);
-int acc_prepare_det(Engine *e);      // deterministic mode: allocate / scale the fixed-point accumulator before a kernel adds to it
+int acc_prepare_det(Engine *e, double q_arriving = 0);      // deterministic mode: allocate / scale the fixed-point accumulator before a kernel adds to it
+                                                             // (q_arriving: the largest |q| of injector records about to be appended, looked at only while no other charge is known)
 int acc_finalize(Engine *e);         // ... and round its sums into the float accumulator before anything reads that
 void host_will_read(const void *p, size_t bytes);   // see engine.hip: called before a HIP copy reads / writes caller memory
 void host_will_write(void *p, size_t bytes);

@@ -141,7 +141,7 @@ static double fixed_scale(double largest) {
   (void)frexp(largest, &ex);
   return ldexp(1.0, 37 - ex);
 }
-int acc_prepare_det(Engine *e) {
+int acc_prepare_det(Engine *e, double q_arriving) {
   if (!e->acc64) {
     VH_CHECK(hipMalloc(&e->acc64, sizeof(unsigned long long) * 12 * (size_t)e->gk.nv));
     VH_CHECK(hipMemsetAsync(e->acc64, 0, sizeof(unsigned long long) * 12 * (size_t)e->gk.nv, e->stream));
@@ -149,6 +149,8 @@ int acc_prepare_det(Engine *e) {
   if (e->acc_scale == 0) {
     double q = e->acc_qref;
     if (!(q > 0)) for (auto &s : e->species) q = std::max(q, (double)s.q_max);
+    if (!(q > 0)) q = q_arriving;                        // the first charge this domain sees comes from a neighbour
+    if (!(q > 0) && q_arriving < 0) return 0;            // ... and what arrives now carries none: its deposits are zeros at any scale, the choice stays open
     if (!(q > 0)) VH_FAIL("deterministic accumulation: no macro-particle charge is known yet (give vpic_hip_set_accumulation a reference charge)");
     e->acc_scale = fixed_scale(4.2 * q);
   }

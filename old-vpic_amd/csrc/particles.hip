@@ -973,10 +973,14 @@ __global__ void exchange_unpark_kernel(int *__restrict__ counters, const RetryMo
   __syncthreads();
   if (threadIdx.x == 0) counters[C_RETRY] = 0;
 }
-// header of an exchange message: {injectors in the payload, 0, 0, 0}
+// header of an exchange message: {injectors in the payload, injectors wanted, 0, 0}.  The slot counter of EVERY face starts
+// the next round at zero: a face closed for this round (no message) has counted the movers it parked, and a message it is
+// given in a later round of the same step is filled from its first slot.
 __global__ void exchange_header_kernel(int *__restrict__ counters, int *const *__restrict__ hdr, const int *__restrict__ cap) {
   const int f = threadIdx.x;
-  if (f < 6 && hdr[f]) { hdr[f][0] = min(counters[C_SEND + f], cap[f]); hdr[f][1] = counters[C_SEND + f]; hdr[f][2] = 0; hdr[f][3] = 0; counters[C_SEND + f] = 0; }
+  if (f >= 6) return;
+  if (hdr[f]) { hdr[f][0] = min(counters[C_SEND + f], cap[f]); hdr[f][1] = counters[C_SEND + f]; hdr[f][2] = 0; hdr[f][3] = 0; }
+  counters[C_SEND + f] = 0;
 }
 __global__ void boundary_backfill_kernel(ParticlesK p, int64_t *tag, int64_t *tag2, const int *__restrict__ counters,
                                          const int *__restrict__ holes, const int *__restrict__ fills) {
@@ -1103,6 +1107,13 @@ void boundary_inject_kernel(const SpeciesTable *__restrict__ Tp, const vpic_part
     }
   }
   if (idx >= Tp->max_np[s]) { atomicOr(&counters[C_OVER], 4); return; }   // counted; the host reports the overflow
+  {
+    // the largest finite |q| appended to the species (Species::q_max follows it, engine.h; the bits of a non-negative float
+    // order as unsigned integers).  The plain read only spares the atomic once the word has caught up.
+    const unsigned qb = __float_as_uint(fabsf(inj.q));
+    unsigned *top = reinterpret_cast<unsigned *>(counters + C_QTOP + s);
+    if (qb < 0x7f800000u && qb > *top) atomicMax(top, qb);
+  }
   float dx = inj.dx, dy = inj.dy, dz = inj.dz, ux = inj.ux, uy = inj.uy, uz = inj.uz;
   float mx = inj.dispx, my = inj.dispy, mz = inj.dispz;
   int pi = inj.i;
@@ -1124,6 +1135,47 @@ void boundary_inject_kernel(const SpeciesTable *__restrict__ Tp, const vpic_part
   }
 }
 
+// Deterministic accumulation whose scale is still open and no charge known on this domain (nothing loaded, no q_ref): the
+// scale comes from the records about to be appended -- the largest finite |q| among the first min(*n_dev, n) of them that
+// name a species.  One small launch and one read-back, once in an engine's life at the most.
+__global__ __launch_bounds__(256)
+void injector_q_top_kernel(const vpic_particle_injector_t *__restrict__ in, int n, const int *__restrict__ n_dev, int n_species,
+                           unsigned *__restrict__ top) {
+  if (n_dev) n = min(*n_dev, n);
+  unsigned best = 0;
+  for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += gridDim.x * 256) {
+    const unsigned qb = __float_as_uint(fabsf(in[t].q));
+    if (in[t].sp_id >= 0 && in[t].sp_id < n_species && qb < 0x7f800000u && qb > best) best = qb;
+  }
+  if (best) atomicMax(top, best);
+}
+static int prepare_det_for_arrivals(Engine *e, const vpic_particle_injector_t *inj, int n, const int *n_dev) {
+  bool known = e->acc_scale != 0 || e->acc_qref > 0;
+  for (auto &s : e->species) known = known || s.q_max > 0;
+  if (known) return acc_prepare_det(e);
+  unsigned *top = reinterpret_cast<unsigned *>(e->counters + C_QMSG), bits = 0;
+  VH_CHECK(hipMemsetAsync(top, 0, sizeof(unsigned), e->stream));
+  hipLaunchKernelGGL(injector_q_top_kernel, dim3(std::min((n + 255) / 256, 64)), dim3(256), 0, e->stream, inj, n, n_dev,
+                     (int)e->species.size(), top);
+  VH_CHECK(hipGetLastError());
+  VH_CHECK(hipMemcpyAsync(e->host_counters + C_QMSG, top, sizeof(unsigned), hipMemcpyDeviceToHost, e->stream));
+  VH_CHECK(hipStreamSynchronize(e->stream));
+  memcpy(&bits, e->host_counters + C_QMSG, sizeof bits);
+  float q;
+  memcpy(&q, &bits, sizeof q);
+  return acc_prepare_det(e, q > 0 ? (double)q : -1.0);
+}
+// (the scale handed to the injection kernel: 1 while the choice is open -- only records without charge are appended then)
+static double det_scale_for_arrivals(const Engine *e) { return !e->det_acc ? 0.0 : e->acc_scale != 0 ? e->acc_scale : 1.0; }
+
+// the largest |q| the injection kernel appended to species k (host_counters holds the device's C_QTOP words) goes into
+// Species::q_max like every charge the host uploads
+static void book_arrived_charge(Engine *e, Species &s, int k) {
+  float q;
+  memcpy(&q, e->host_counters + C_QTOP + k, sizeof q);
+  if (q > s.q_max) s.q_max = q;
+}
+
 int k_boundary_p_inject(Engine *e, const vpic_particle_injector_t *inj, int n, const int64_t *tags) {
   if (n <= 0) return 0;
   const int ns = (int)e->species.size();
@@ -1143,17 +1195,21 @@ int k_boundary_p_inject(Engine *e, const vpic_particle_injector_t *inj, int n, c
   if (ensure_stage(e, sizeof(SpeciesTable))) return 1;
   VH_CHECK(hipMemcpyAsync(e->stage, &T, sizeof(SpeciesTable), hipMemcpyHostToDevice, e->stream));
   VH_CHECK(hipStreamSynchronize(e->stream));     // T lives on this stack frame
-  if (e->det_acc && acc_prepare_det(e)) return 1;
+  if (e->det_acc && prepare_det_for_arrivals(e, inj, n, nullptr)) return 1;
+  // (the C_QTOP words are not cleared here: they only grow, and a call in the middle of a resident exchange must not drop what
+  // that step's messages have brought so far)
   hipLaunchKernelGGL(boundary_inject_kernel, dim3((n + 255) / 256), dim3(256), 0, e->stream,
                      (const SpeciesTable *)e->stage, inj, n, e->gk,
                      e->det_acc ? reinterpret_cast<float *>(e->acc64) : reinterpret_cast<float *>(e->acc), e->counters, tags,
-                     (const int *)nullptr, e->det_acc ? e->acc_scale : 0.0);
+                     (const int *)nullptr, det_scale_for_arrivals(e));
   VH_CHECK(hipGetLastError());
   VH_CHECK(hipMemcpyAsync(e->host_counters + C_NP, e->counters + C_NP, sizeof(int) * (2 * MAX_SPECIES + 1), hipMemcpyDeviceToHost, e->stream));
+  VH_CHECK(hipMemcpyAsync(e->host_counters + C_QTOP, e->counters + C_QTOP, sizeof(int) * MAX_SPECIES, hipMemcpyDeviceToHost, e->stream));
   VH_CHECK(hipStreamSynchronize(e->stream));
   for (int k = 0; k < ns; k++) {
     Species &s = e->species[k];
     if (e->host_counters[C_CHARGED] >> k & 1) s.chargeless = false;
+    book_arrived_charge(e, s, k);
     const int64_t np = e->host_counters[C_NP + k], nm = e->host_counters[C_NMS + k];
     if (np > s.max_np) VH_FAIL("boundary_p: species %d needs %lld particle slots, has %lld (the reference would grow the array, boundary_p.c:416-432)", k, (long long)np, (long long)s.max_np);
     if (nm > s.max_nm) VH_FAIL("boundary_p: species %d needs %lld mover slots, has %lld", k, (long long)nm, (long long)s.max_nm);
@@ -1196,6 +1252,7 @@ int k_exchange_begin(Engine *e) {
   VH_CHECK(hipMemsetAsync(e->counters + C_SEND, 0, sizeof(int) * 6, e->stream));
   VH_CHECK(hipMemsetAsync(e->counters + C_CHARGED, 0, sizeof(int) * 3, e->stream));      // charged species, overflow flags, parked movers
   VH_CHECK(hipMemsetAsync(e->counters + C_NHOLE, 0, sizeof(int) * MAX_SPECIES, e->stream));   // (dead slots made THIS step; the host keeps the total)
+  VH_CHECK(hipMemsetAsync(e->counters + C_QTOP, 0, sizeof(int) * MAX_SPECIES, e->stream));    // (the largest |q| that arrives THIS step; booked by _finish)
   if (!e->retry_buf) VH_CHECK(hipMalloc(&e->retry_buf, sizeof(RetryMover) * RETRY_CAP));
   return upload_species_table(e);
 }
@@ -1257,13 +1314,14 @@ int k_exchange_pack(Engine *e, void *const msg[6], const int32_t cap[6], int mov
 
 int k_exchange_inject(Engine *e, const void *msg, int cap) {
   if (cap < 1 || !msg) VH_FAIL("Bad exchange message");
+  if (!e->sp_table_dev) VH_FAIL("vpic_hip_exchange_inject before vpic_hip_exchange_begin");     // (the kernel reads the species table _begin uploads)
   const int *hdr = reinterpret_cast<const int *>(msg);
   const vpic_particle_injector_t *inj = reinterpret_cast<const vpic_particle_injector_t *>(reinterpret_cast<const char *>(msg) + 16);
-  if (e->det_acc && acc_prepare_det(e)) return 1;
+  if (e->det_acc && prepare_det_for_arrivals(e, inj, cap, hdr)) return 1;
   hipLaunchKernelGGL(boundary_inject_kernel, dim3((cap + 255) / 256), dim3(256), 0, e->stream,
                      (const SpeciesTable *)e->sp_table_dev, inj, cap, e->gk,
                      e->det_acc ? reinterpret_cast<float *>(e->acc64) : reinterpret_cast<float *>(e->acc), e->counters, (const int64_t *)nullptr, hdr,
-                     e->det_acc ? e->acc_scale : 0.0);
+                     det_scale_for_arrivals(e));
   VH_CHECK(hipGetLastError());
   return 0;
 }
@@ -1283,6 +1341,7 @@ int k_exchange_finish(Engine *e, const void *const *recv, int n_recv, int32_t *h
   for (size_t k = 0; k < e->species.size(); k++) {
     Species &s = e->species[k];
     if (e->host_counters[C_CHARGED] >> k & 1) s.chargeless = false;
+    book_arrived_charge(e, s, (int)k);
     const int64_t np = e->host_counters[C_NP + k], nm = e->host_counters[C_NMS + k], gone = e->host_counters[C_NHOLE + k];
     if (np != s.np || gone) s.partition_valid = false;
     s.np = np > s.max_np ? s.max_np : np; s.nm = nm > s.max_nm ? s.max_nm : nm; s.n_holes += gone;
