@@ -21,6 +21,11 @@
 //     loads and stores remain coalesced;
 //   * the 12 accumulator components are summed over each run with a segmented DPP scan in registers (v_fmac_f32 with
 //     a DPP source per component and step) and only the last lane of a run issues LDS atomics;
+//   * what a lane forms, the scan sums and a float window holds are not the 12 deposit terms but the 12 MOMENTS they are
+//     a +-1 combination of (push_device.h: streak12_moments; half the instructions per particle).  The map is applied where a
+//     value leaves for the global accumulator, which stays in term form: at the flush (once per window cell, in the window's
+//     precision), and in registers where a run total misses the window (deposit_run: on the spot or by way of the miss list).
+//     All float windows do so, the row windows Window<0> / Window<1> included; the deterministic instances keep the terms;
 //   * the accumulators of the tile and its halo (6x6x6 cells: every cell a particle of the tile can reach in a step,
 //     and for several steps after the sort) live in LDS in double precision and are flushed once per workgroup with
 //     coalesced global float atomics; a deposit outside the window goes to the global accumulator directly;
@@ -181,7 +186,7 @@ __device__ __forceinline__ void hist_count(const HistK &h, int key, int wbase, i
 }
 
 template <class W>
-__device__ __forceinline__ void deposit_run(const bool tail, const float (&a)[12], int key, int lane, typename W::acc_t *s_acc, float *g_acc,
+__device__ __forceinline__ void deposit_run(const bool tail, float (&a)[12], int key, int lane, typename W::acc_t *s_acc, float *g_acc,
                                             int wbase, int sy, int sz, const TileDiv &td, MissList *ml, int &n_miss, const int pre_slot = -2) {
   const int slot = pre_slot != -2 ? pre_slot : slot_of<W>(key, wbase, sy, sz, td);   // (pre_slot: the caller has it already)
   if constexpr (is_det<W>::value) {                 // (integer sums: a miss goes straight to the global words, in any order)
@@ -192,6 +197,11 @@ __device__ __forceinline__ void deposit_run(const bool tail, const float (&a)[12
   const bool miss = tail && slot < 0;
   const unsigned long long mm = __ballot(miss);
   if (mm) {                                                    // wave-uniform, rare
+    // A float window holds MOMENTS, the global accumulator TERMS (push_device.h): a run total that leaves for global memory from
+    // here -- on the spot or by way of the list -- becomes terms now, in its lane's registers.  (In place: the caller is done
+    // with them.  Expanded by flush_misses instead, four list entries a lane, the hot instance needed a granule of registers
+    // more and lost a wavefront per SIMD; so the list holds terms.)
+    if (miss) moments_to_terms(a, a);
     const int cnt = __popcll(mm);
     if (cnt > MISS_CAP) {                                      // more than the list holds: on the spot
       if (miss) deposit12<true, W>(s_acc, g_acc, key, -1, a);
@@ -349,33 +359,19 @@ constexpr int FLIP_SHIFT = 28;
 __device__ __forceinline__ float fast_rsq(float x) { return __builtin_amdgcn_rsqf(x); }
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
-// the 12 streak terms with contracted multiply-adds (same formula as streak12, push_device.h)
-__device__ __forceinline__ void streak12_fast(float *a, float q, float dx, float dy, float dz,
-                                              float ux, float uy, float uz) {
-  const float xp = 1.f + dx, xm = 1.f - dx, yp = 1.f + dy, ym = 1.f - dy, zp = 1.f + dz, zm = 1.f - dz;
-  const float qx = q * ux, qy = q * uy, qz = q * uz;
-  const float v5 = (qx * uy) * (uz * (1.f / 3.f));
-  float v0, v1;
-  v0 = __builtin_fmaf(-qx, dy, qx); v1 = __builtin_fmaf(qx, dy, qx);
-  a[0] = __builtin_fmaf(v0, zm, v5); a[1] = __builtin_fmaf(v1, zm, -v5); a[2] = __builtin_fmaf(v0, zp, -v5); a[3] = __builtin_fmaf(v1, zp, v5);
-  v0 = __builtin_fmaf(-qy, dz, qy); v1 = __builtin_fmaf(qy, dz, qy);
-  a[4] = __builtin_fmaf(v0, xm, v5); a[5] = __builtin_fmaf(v1, xm, -v5); a[6] = __builtin_fmaf(v0, xp, -v5); a[7] = __builtin_fmaf(v1, xp, v5);
-  v0 = __builtin_fmaf(-qz, dx, qz); v1 = __builtin_fmaf(qz, dx, qz);
-  a[8] = __builtin_fmaf(v0, ym, v5); a[9] = __builtin_fmaf(v1, ym, -v5); a[10] = __builtin_fmaf(v0, yp, -v5); a[11] = __builtin_fmaf(v1, yp, v5);
-}
-
-// The 12 terms of one segment of a cell-crosser in the arithmetic instance W deposits with.  The DETERMINISTIC instances
-// form them as the reference does, operation by operation (push_device.h: streak12; v5 as move_p.c:76 has it, the last
+// What one segment of a cell-crosser deposits, in the form instance W sums.  The DETERMINISTIC instances form the 12 terms
+// as the reference does, operation by operation (push_device.h: streak12; v5 as move_p.c:76 has it, the last
 // multiply in double): every word of their integer sums is then what an order-free computation on the reference's own floats
-// predicts, which tests/test_gpu_det_exact.py checks exactly.  The float instances keep the contracted form: their sums
-// are rounded in an order of the machine's choosing anyway.
+// predicts, which tests/test_gpu_det_exact.py checks exactly.  The float instances form the 12 MOMENTS the terms are linear
+// in (push_device.h: streak12_moments; the terms with contracted multiply-adds took twice the instructions): their windows
+// hold moments, and their sums are rounded in an order of the machine's choosing anyway.
 template <class W>
 __device__ __forceinline__ void mover_streak12(float *a, float q, float mx, float my, float mz, float sx, float sy, float sz) {
   if constexpr (is_det<W>::value) {
     const float v5 = (float)((double)(q * sx * sy * sz) * (1. / 3.));
     streak12(a, q, mx, my, mz, sx, sy, sz, v5);
   } else {
-    streak12_fast(a, q, mx, my, mz, sx, sy, sz);
+    streak12_moments(a, q, mx, my, mz, sx, sy, sz);
   }
 }
 
@@ -1028,13 +1024,14 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
       }
       if (!CHARGELESS && !(ablate & 1)) {
         const float qd = (incell && active) ? q : 0.f;
-        // The 12 deposit terms with contracted multiply-adds in BOTH arithmetic modes of the float instances: they are summed
-        // in an order of the machine's choosing anyway (the accumulators agree with the reference's to 2e-6 of the largest
-        // entry, not bit for bit), each term is within a few ulp of the reference's, and no particle state depends on them
-        // (+1.3 % measured).  The DETERMINISTIC instances form them as advance_p.cxx:131-162 does, operation by operation:
+        // The float instances form the 12 deposit MOMENTS (push_device.h), with contracted multiply-adds in BOTH arithmetic
+        // modes: the sums are made in an order of the machine's choosing anyway (the accumulators agree with the reference's
+        // to 2e-6 of the largest entry, not bit for bit), the terms the flush forms from the summed moments are no further from
+        // the reference's than summed terms were (tests/test_deposit_moments_ref.py), and no particle state depends on them.
+        // The DETERMINISTIC instances form the terms as advance_p.cxx:131-162 does, operation by operation:
         // their sums are exact, and exactly those of the reference's floats (tests/test_gpu_det_exact.py).
         if constexpr (is_det<W>::value) streak12(a, qd, v0, v1, v2, ux, uy, uz, qd * ux * uy * uz * one_third);
-        else streak12_fast(a, qd, v0, v1, v2, ux, uy, uz);
+        else streak12_moments(a, qd, v0, v1, v2, ux, uy, uz);
       } else {
 #pragma unroll
         for (int k = 0; k < 12; k++) a[k] = 0.f;
@@ -1144,7 +1141,7 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
     }
   }
   const int k = tid % 12, c0 = tid / 12;
-  if (DET) {
+  if constexpr (DET) {
     if (TILE && wbase != NO_WINDOW && tid < 12 * FLUSH_CELLS) {
       unsigned long long *g64 = reinterpret_cast<unsigned long long *>(g_acc);
       for (int cell = c0; cell < W::NSLOT; cell += FLUSH_CELLS) {
@@ -1153,22 +1150,27 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
         if (v) atomicAdd(g64 + (size_t)(wbase + lx + gsy * ly + gsz * lz) * 12 + k, v);
       }
     }
-  } else if (TILE) {
+  } else if constexpr (TILE) {
+    // the window holds MOMENTS (push_device.h): thread k forms its term from the four moments of its group, in the window's
+    // precision, then converts and adds; what is skipped is a term that is zero
     if (wbase != NO_WINDOW && tid < 12 * FLUSH_CELLS) {
+      const TermSigns sg = term_signs(k & 3);
+      const acc_t *src = s_acc + (k & ~3) * NSLOT_PAD;
       for (int cell = c0; cell < W::NSLOT; cell += FLUSH_CELLS) {
-        const float v = (float)s_acc[k * NSLOT_PAD + cell];
+        const float v = (float)term_of(sg, src[cell], src[NSLOT_PAD + cell], src[2 * NSLOT_PAD + cell], src[3 * NSLOT_PAD + cell]);
         const int lx = cell % WX, lyz = cell / WX, ly = lyz % WX, lz = lyz / WX;
         if (v != 0.f) atomicAdd(g_acc + (size_t)(wbase + lx + gsy * ly + gsz * lz) * 12 + k, v);
       }
     }
   } else if (tid < 12 * FLUSH_CELLS) {
+    const TermSigns sg = term_signs(k & 3);                // (the row windows hold moments as well)
 #pragma unroll
     for (int s = 0; s < NSEG; s++) {
       const int seg_base = wbase + ((s == 0) ? 0 : (s == 1) ? gsy : (s == 2) ? -gsy : (s == 3) ? gsz : -gsz);
-      const acc_t *src = s_acc + k * NSLOT_PAD + s * WX;
+      const acc_t *src = s_acc + (k & ~3) * NSLOT_PAD + s * WX;
       float *dst = g_acc + (size_t)seg_base * 12 + k;
       for (int cell = c0; cell < WX; cell += FLUSH_CELLS) {
-        const float v = (float)src[cell];                  // the workgroup's total
+        const float v = (float)term_of(sg, src[cell], src[NSLOT_PAD + cell], src[2 * NSLOT_PAD + cell], src[3 * NSLOT_PAD + cell]);   // the workgroup's total
         if (v != 0.f) atomicAdd(dst + cell * 12, v);
       }
     }

@@ -126,7 +126,13 @@ __device__ __forceinline__ int slot_of(int key, int wbase, int sy, int sz, const
     const unsigned lz = __umulhi(rel, td.mul_sz) >> td.sh_sz, r2 = rel - lz * (unsigned)sz;
     const unsigned ly = __umulhi(r2, td.mul_sy) >> td.sh_sy, lx = r2 - ly * (unsigned)sy;
     const bool in = wbase != NO_WINDOW && (int)rel >= 0 && lz < (unsigned)W::WX && ly < (unsigned)W::WX && lx < (unsigned)W::WX;
-    return in ? (int)(lx + (unsigned)W::WX * (ly + (unsigned)W::WX * lz)) : -1;
+    // (24-bit multiply-adds, stated: the compiler makes a 32-bit one a v_mad_u64_u32, quarter rate and a register pair, and
+    // turns __umul24 back into that.  The coordinates of a slot that is used are below WX; what the others give becomes -1)
+    static_assert(W::WX <= 64, "an inline constant");
+    unsigned slot;
+    asm("v_mad_u32_u24 %0, %1, %3, %2" : "=v"(slot) : "v"(lz), "v"(ly), "n"(W::WX));
+    asm("v_mad_u32_u24 %0, %1, %3, %2" : "=v"(slot) : "v"(slot), "v"(lx), "n"(W::WX));
+    return in ? (int)slot : -1;
   } else {
     return window_slot<W::WX>(key, wbase, sy, sz);
   }
@@ -193,6 +199,48 @@ __device__ __forceinline__ void streak12(float *a, float q, float dx, float dy, 
   ACCUMULATE_J(y, z, x, 4);
   ACCUMULATE_J(z, x, y, 8);
 #undef ACCUMULATE_J
+}
+
+// ---- deposit MOMENTS ----------------------------------------------------------------------------------------------------
+// The four terms of an axis group are a +-1 combination of four moments.  For the x group (ACCUMULATE_J(x,y,z) above), with
+// S0 = q ux, S1 = S0 dy, S2 = S0 dz, T3 = S1 dz + v5 (v5 always carries the sign of the dy dz product):
+//   a0 = S0 - S1 - S2 + T3      a1 = S0 + S1 - S2 - T3      a2 = S0 - S1 + S2 - T3      a3 = S0 + S1 + S2 + T3
+// and cyclically for y and z.  Everything between a particle's arithmetic and the global accumulator is a sum (the segmented
+// scan, the LDS atomics of the run tails, the window), and a linear map commutes with sums: the FLOAT instances
+// (Window<0> .. Window<3>) form, scan and keep the twelve moments -- 15 vector instructions a particle where the terms take
+// 30 -- and apply the map where a value leaves for the global accumulator, which stays in term form: once per window cell at
+// the flush, and in registers where a run total misses the window and goes to global memory (push.hip: deposit_run).
+// The moments sit in accumulator order, (T3, S1, S2, S0) in the four slots of their group: in that order the map is a
+// symmetric matrix, its own inverse up to the factor 4.  The DETERMINISTIC instances (Window<4> .. Window<6>) and move_p_lane
+// keep the terms: streak12, operation by operation.
+__device__ __forceinline__ void streak12_moments(float *m, float q, float dx, float dy, float dz, float ux, float uy, float uz) {
+  const float qx = q * ux, qy = q * uy, qz = q * uz;
+  const float v5 = (qx * uy) * (uz * (1.f / 3.f));
+  m[3] = qx; m[1] = qx * dy; m[2] = qx * dz; m[0] = __builtin_fmaf(m[1], dz, v5);
+  m[7] = qy; m[5] = qy * dz; m[6] = qy * dx; m[4] = __builtin_fmaf(m[5], dx, v5);
+  m[11] = qz; m[9] = qz * dx; m[10] = qz * dy; m[8] = __builtin_fmaf(m[9], dy, v5);
+}
+
+// term j (0 .. 3) of a group from the moments m0 .. m3 in its four slots: a_j = (S0 + s1 s2 T3) + (s1 S1 + s2 S2), s1 = +1 for
+// odd j, s2 = +1 for j >= 2.  The signs are applied as sign-bit masks, fixed per thread where the thread's component is.
+struct TermSigns { unsigned s1, s2, s3; };
+__device__ __forceinline__ TermSigns term_signs(int j) {
+  const unsigned neg = 0x80000000u;
+  TermSigns s = {(j & 1) ? 0u : neg, (j & 2) ? 0u : neg, (((j >> 1) ^ j) & 1) ? neg : 0u};
+  return s;
+}
+__device__ __forceinline__ float with_sign(float v, unsigned s) { return __int_as_float(__float_as_int(v) ^ (int)s); }
+__device__ __forceinline__ double with_sign(double v, unsigned s) { return __longlong_as_double(__double_as_longlong(v) ^ (long long)((unsigned long long)s << 32)); }
+template <class T> __device__ __forceinline__ T term_of(const TermSigns &s, T m0, T m1, T m2, T m3) {
+  return (m3 + with_sign(m0, s.s3)) + (with_sign(m1, s.s1) + with_sign(m2, s.s2));
+}
+// all twelve at once, in registers (the same sums as term_of: 24 additions); a may be m
+__device__ __forceinline__ void moments_to_terms(float *a, const float *m) {
+#pragma unroll
+  for (int g = 0; g < 12; g += 4) {
+    const float p03 = m[g + 3] + m[g], m03 = m[g + 3] - m[g], p12 = m[g + 1] + m[g + 2], m12 = m[g + 1] - m[g + 2];
+    a[g] = p03 - p12; a[g + 1] = m03 + m12; a[g + 2] = m03 - m12; a[g + 3] = p03 + p12;
+  }
 }
 
 // move_p.c:34-134 for one lane.  Returns 1 when the particle stopped on a face this domain
