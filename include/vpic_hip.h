@@ -308,7 +308,7 @@ int vpic_hip_energy_p(vpic_hip_engine_t *e, int sp, double *energy); /* species_
  * angle.  It is NON-RELATIVISTIC in u (u is taken for the velocity in units of c: valid for |u| << 1; there is no Lorentz
  * factor anywhere), rank-local (a cell's particles are all on this rank), and its result depends on the order of the array
  * within a cell (the pairing is by position in the cell's range): statistically the same in any order, bit for bit only
- * for the same array.  A relativistic (Perez-style) form is out of scope.
+ * for the same array.  The relativistic (Perez) form of the pair is vpic_hip_collide_relativistic, below.
  * THE RULE, a contract (tests/collide_ref.py restates it in numpy; tests/test_gpu_collide.py holds every word to it):
  *   mix32(x):  x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16   (uint32, a bijection)
  *   Cells are the interior voxels v = x + (nx+2) * (y + (ny+2) * z), 1 <= x <= nx ...; the particles of species s in cell v
@@ -384,6 +384,56 @@ int vpic_hip_collide_instance(vpic_hip_engine_t *e, int *instance);
 /* parity tests: the four draws of every pair from a table in host memory, 4 floats per particle index (see above); n = 0
  * switches back to the counter stream */
 int vpic_hip_set_collide_draws(vpic_hip_engine_t *e, const float *draws, int64_t n);
+/* ---- the same collisions with the RELATIVISTIC pair of Perez et al., Phys. Plasmas 19, 083104 (2012), sections II A and B ----
+ * u is the momentum per mass in units of c, as everywhere else in this library.  The pair is taken to its centre-of-momentum
+ * frame, turned there by an angle whose variance carries the relativistic factors, and taken back: every pair of equal
+ * weights keeps m_f u_f + m_s u_s and m_f gamma_f + m_s gamma_s (up to rounding).  An opt-in model: vpic_hip_collide is
+ * bit for bit what it was.
+ * SHARED with vpic_hip_collide, word for word (THE RULE above): the descriptor and its argument errors, the exact ranges or
+ * the sort first, the cap, mix32, the cells, c0, the keys and perm, the pairs of one species (the triple of an odd cell with
+ * s2 halved), the L / S pairs of two species, N, w, the first particle of a pair, the four draws per pair and where they
+ * come from (counter stream or vpic_hip_set_collide_draws), the weight rule (do_f, do_s below are the two conditions above),
+ * the order in which pairs that share a particle are applied, what the call touches, the two kernel instances,
+ * vpic_hip_collide_stats (out[2] also counts the pairs the two skips below leave alone) and vpic_hip_collide_instance.
+ * Only PER PAIR differs.  (tests/collide_rel_ref.py restates it in numpy; tests/test_gpu_collide_rel.py holds every word to it.)
+ *   Per pair (first f, second s): the float momenta, masses, weights w, cvar, dt, V = (dx * dy) * dz (that float product), N
+ *   and the four draws are promoted to double; every operation below is IEEE double, rounded once, unfused, / and sqrt
+ *   correctly rounded, the parentheses as written; the two new momenta are rounded to float once each, at the end.
+ *     ux_f == ux_s && uy_f == uy_s && uz_f == uz_s (compared as floats): the pair is skipped (and counted); otherwise
+ *     g_f = sqrt(1 + ((ux_f*ux_f + uy_f*uy_f) + uz_f*uz_f));  g_s likewise                              (the Lorentz factors)
+ *     e_f = m_f * g_f;  e_s = m_s * g_s;  E = e_f + e_s;  rE = 1 / E
+ *     vx = (m_f*ux_f + m_s*ux_s) * rE;  vy, vz likewise                     (v_C = P / E, the velocity of the pair's frame)
+ *     gC = 1 / sqrt(1 - ((vx*vx + vy*vy) + vz*vz));  kC = (gC * gC) / (gC + 1)      (kC = (gC - 1) / v_C^2 without its cancellation)
+ *     vu_f = (vx*ux_f + vy*uy_f) + vz*uz_f;  vu_s likewise
+ *     c_f = kC * vu_f - gC * g_f
+ *     px = m_f * (ux_f + c_f * vx);  py, pz likewise                      (p*, the first particle's momentum in that frame)
+ *     es_f = m_f * (gC * (g_f - vu_f));  es_s = m_s * (gC * (g_s - vu_s))                   (m gamma* of each in that frame)
+ *     pq = px*px + py*py;  p2 = pq + pz*pz;  pm = sqrt(p2);  gp = sqrt(pq)
+ *     pm == 0: the pair is skipped (and counted); otherwise
+ *     r = (es_f * es_s) / (pm * pm) + 1
+ *     s2 = ((((cvar * max(w_f, w_s)) * N) * dt) * (((gC * pm) * rE) * (r * r))) / (V * (e_f * e_s));  in the triple s2 = 0.5 * s2
+ *          (max(w_f, w_s) taken of the floats.  Perez eq. 21: the variance of tan(theta / 2); for |u| -> 0 it is the s2 above)
+ *     d = draw_N * sqrt(s2);  t = d * d
+ *     t < 2^64:  sin_t = (2 * d) / (1 + t),  omc = (2 * t) / (1 + t);   otherwise (a NaN included):  sin_t = 0,  omc = 2
+ *     sc = sin_t * cos_phi;  ss = sin_t * sin_phi
+ *     gp != 0:  ax = px / gp;  ay = py / gp
+ *               Dx = ((ax * pz) * sc - (ay * pm) * ss) - px * omc
+ *               Dy = ((ay * pz) * sc + (ax * pm) * ss) - py * omc
+ *               Dz = (-(gp * sc)) - pz * omc
+ *     gp == 0:  Dx = pm * sc;  Dy = pm * ss;  Dz = -(pz * omc)
+ *     qx = px + Dx;  qy, qz likewise                                                   (p* turned: |q| = |p*|)
+ *     kvq = kC * ((vx*qx + vy*qy) + vz*qz)
+ *     a_f = kvq + es_f * gC;   u_f = (float)((q + v * a_f) * (1 / m_f))      componentwise, ((qx + vx * a_f) * (1 / m_f)), done iff do_f
+ *     a_s = es_s * gC - kvq;   u_s = (float)((v * a_s - q) * (1 / m_s))      componentwise, ((vx * a_s - qx) * (1 / m_s)), done iff do_s
+ * Limits.  Rank-local, dependent on the order of the array within a cell, capped at VPIC_HIP_COLLIDE_MAX_CELL, all as above.
+ * The double boost is meant for |u| from about 1e-3 to about 1e3; the tests cover 1e-3 .. 30.  Upwards the boost loses
+ * gC^2 ulps of double in the pair's sum m u and sum m gamma (g_f - v_C.u_f cancels: 1e-10 of E at gC = 1e3, a thousandth of
+ * a float ulp) and 1 - v_C^2 rounds to 0 near gC = 1e8.  Below |u| ~ 1e-3 the result is still right to float rounding in u, but the
+ * energy of a pair is carried as m gamma and kept only to about 1e-16 m gamma / (its kinetic energy): 2e-5 of the kinetic
+ * energy at |u| = 1e-4 and a mass ratio of 1836.  vpic_hip_collide is the better tool there.  Not included: the
+ * low-temperature and maximum-frequency correction of Perez section II C, and a computed Coulomb logarithm (cvar carries
+ * ln(Lambda) as before). */
+int vpic_hip_collide_relativistic(vpic_hip_engine_t *e, const vpic_hip_collision_t *c);
 
 /* ---- energy spectra of a species (the diagnostic of decks/trecon-part/energy.cxx, computed where the particles are) ----
  * One pass over the species' stored momenta (no half-step field correction, unlike energy_p).  Per live particle

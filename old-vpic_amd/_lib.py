@@ -114,6 +114,8 @@ def lib():
         L.vpic_hip_collide_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.vpic_hip_collide_instance.argtypes = [C.c_void_p, C.c_void_p]
         L.vpic_hip_set_collide_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    if hasattr(L, "vpic_hip_collide_relativistic"):         # (... or has them without the relativistic pair)
+        L.vpic_hip_collide_relativistic.argtypes = [C.c_void_p, C.c_void_p]
     L.vpic_hip_dump_gather.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_size_t]
     _lib = L
     return L
@@ -137,4 +139,4 @@ vpic_hip_species_distribution_sums vpic_hip_species_distribution_sums_stats
 vpic_hip_cell_distribution vpic_hip_cell_distribution_stats
 vpic_hip_species_select_count vpic_hip_species_select vpic_hip_species_select_stats
 vpic_hip_accumulate_hydro_p_select
-vpic_hip_collide vpic_hip_collide_stats vpic_hip_collide_instance vpic_hip_set_collide_draws""".split()
+vpic_hip_collide vpic_hip_collide_relativistic vpic_hip_collide_stats vpic_hip_collide_instance vpic_hip_set_collide_draws""".split()

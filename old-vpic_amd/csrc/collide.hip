@@ -5,7 +5,7 @@
 //      no dead slot, the starts a partition of the array; the fullest cell
 //   2  (the host, policy.h: plan_collide)              sorts a species whose ranges are not exact and checks again; refuses a
 //      cell over the cap before anything is written; picks the instance
-//   3  collide_kernel<T, SAME>                          ONE CELL PER WORKGROUP AT A TIME (a workgroup takes every
+//   3  collide_kernel<T, SAME, REL>                     ONE CELL PER WORKGROUP AT A TIME (a workgroup takes every
 //      gridDim.x-th cell).  T = 64: a workgroup of one wavefront, lane =
 //      particle, keys in registers and ranked with cross-lane reads; T = 256: the keys of the cell in LDS, ranked by counting
 //      there.  Both stage the cell's momenta and weights in LDS, apply the pairs there and write the momenta back.
@@ -13,6 +13,7 @@
 // between two species every S particle's pairs j, j + n_S, ... by the ONE thread that owns that S particle, in ascending j
 // -- the "rounds" of the unequal pairing are that thread's loop, so no barrier separates them and no two threads ever write
 // the same particle (an L particle is in exactly one pair).
+// REL = true is vpic_hip_collide_relativistic: the same kernel around another pair function (collide_pair_rel, in double).
 #include "engine.h"
 #include <algorithm>
 
@@ -34,12 +35,12 @@ __device__ __forceinline__ float c_unit(unsigned r) { return ((float)(r >> 8) + 
 struct CollideSpK {
   float *ux, *uy, *uz; const float *q; const int *i; const int *starts;
   int order, np;                     // order: 0 nothing to pair, 1 starts = partition[voxel], 2 starts = tpart[tile key]
-  float wq, f;                       // f = m_ab / m of this species
+  float wq, f;                       // f = m_ab / m of this species (the relativistic model: m itself)
   unsigned id;
 };
 struct CollideK {
   CollideSpK a, b;
-  float cvar, dt, den;               // den = (V * m_ab) * m_ab
+  float cvar, dt, den;               // den = (V * m_ab) * m_ab (the relativistic model: V)
   unsigned seed, call, rank;
   const float *draws;                // test mode: 4 floats per particle index, or null
   unsigned long long *words;
@@ -190,8 +191,61 @@ __device__ __forceinline__ int collide_pair(const CollideK &k, const Slab &F, in
   return do_f && do_s ? PAIR_SCATTERED : PAIR_ONE_SIDED;
 }
 
+// one pair of vpic_hip_collide_relativistic (Perez et al. 2012), include/vpic_hip.h operation by operation: the float momenta,
+// masses, weights and draws promoted to double, every operation in double (unfused; / and sqrt correctly rounded), the two new
+// momenta rounded to float once each.  mf, ms: the masses of the pair's first and second particle; k.den is V here.  gamma
+// is computed from the slab's momenta of this moment: an S particle's change between its pairs.
+__device__ __forceinline__ int collide_pair_rel(const CollideK &k, const Slab &F, int kf, const Slab &S, int ks, float mf_, float ms_, float fN, bool half,
+                                                const Draws &d) {
+  const float fx = F.ux[kf], fy = F.uy[kf], fz = F.uz[kf], sx = S.ux[ks], sy = S.uy[ks], sz = S.uz[ks];
+  if (fx == sx && fy == sy && fz == sz) return PAIR_SKIPPED;
+  const double ufx = fx, ufy = fy, ufz = fz, usx = sx, usy = sy, usz = sz, mf = mf_, ms = ms_;
+  const double gf = sqrt(1.0 + ((ufx * ufx + ufy * ufy) + ufz * ufz)), gs = sqrt(1.0 + ((usx * usx + usy * usy) + usz * usz));
+  const double ef = mf * gf, es = ms * gs, E = ef + es, rE = 1.0 / E;
+  const double vx = (mf * ufx + ms * usx) * rE, vy = (mf * ufy + ms * usy) * rE, vz = (mf * ufz + ms * usz) * rE;
+  const double gC = 1.0 / sqrt(1.0 - ((vx * vx + vy * vy) + vz * vz)), kC = (gC * gC) / (gC + 1.0);
+  const double vuf = (vx * ufx + vy * ufy) + vz * ufz, vus = (vx * usx + vy * usy) + vz * usz;
+  const double cf = kC * vuf - gC * gf;
+  const double px = mf * (ufx + cf * vx), py = mf * (ufy + cf * vy), pz = mf * (ufz + cf * vz);
+  const double esf = mf * (gC * (gf - vuf)), ess = ms * (gC * (gs - vus));          // m gamma* of each in the pair's frame
+  const double pq = px * px + py * py, p2 = pq + pz * pz, pm = sqrt(p2), gp = sqrt(pq);
+  if (pm == 0.0) return PAIR_SKIPPED;
+  const float wf = F.w[kf], ws = S.w[ks];
+  const double r = (esf * ess) / (pm * pm) + 1.0;
+  double s2 = (((((double)k.cvar * (double)fmaxf(wf, ws)) * (double)fN) * (double)k.dt) * (((gC * pm) * rE) * (r * r))) / ((double)k.den * (ef * es));
+  if (half) s2 = 0.5 * s2;
+  const double dl = (double)d.n * sqrt(s2), t = dl * dl;
+  double sin_t = 0.0, omc = 2.0;
+  if (t < 18446744073709551616.0) { sin_t = (2.0 * dl) / (1.0 + t); omc = (2.0 * t) / (1.0 + t); }
+  const double sc = sin_t * (double)d.c, ss = sin_t * (double)d.s;
+  double Dx, Dy, Dz;
+  if (gp != 0.0) {
+    const double ax = px / gp, ay = py / gp;
+    Dx = ((ax * pz) * sc - (ay * pm) * ss) - px * omc;
+    Dy = ((ay * pz) * sc + (ax * pm) * ss) - py * omc;
+    Dz = (-(gp * sc)) - pz * omc;
+  } else { Dx = pm * sc; Dy = pm * ss; Dz = -(pz * omc); }
+  const double qx = px + Dx, qy = py + Dy, qz = pz + Dz;
+  const double kvq = kC * ((vx * qx + vy * qy) + vz * qz);
+  const bool do_f = ws >= wf || d.u * wf < ws, do_s = wf >= ws || d.u * ws < wf;
+  if (do_f) {
+    const double a = kvq + esf * gC, rm = 1.0 / mf;
+    F.ux[kf] = (float)((qx + vx * a) * rm); F.uy[kf] = (float)((qy + vy * a) * rm); F.uz[kf] = (float)((qz + vz * a) * rm);
+  }
+  if (do_s) {
+    const double a = ess * gC - kvq, rm = 1.0 / ms;
+    S.ux[ks] = (float)((vx * a - qx) * rm); S.uy[ks] = (float)((vy * a - qy) * rm); S.uz[ks] = (float)((vz * a - qz) * rm);
+  }
+  return do_f && do_s ? PAIR_SCATTERED : PAIR_ONE_SIDED;
+}
+// the pair of a kernel instance: ff, fs are m_ab / m of the two particles (REL: their masses)
+template <bool REL>
+__device__ __forceinline__ int pair_of(const CollideK &k, const Slab &F, int kf, const Slab &S, int ks, float ff, float fs, float fN, bool half, const Draws &d) {
+  return REL ? collide_pair_rel(k, F, kf, S, ks, ff, fs, fN, half, d) : collide_pair(k, F, kf, S, ks, ff, fs, fN, half, d);
+}
+
 extern __shared__ unsigned collide_lds[];
-template <int T, bool SAME>
+template <int T, bool SAME, bool REL>
 __global__ __launch_bounds__(T) void collide_kernel(CollideK k, unsigned n_cells) {
   __shared__ unsigned s_cnt[3];
   const Slab A = slab_at(collide_lds, k.stride), B = slab_at(collide_lds + (SAME ? 0 : COLLIDE_SLAB_ARRAYS * k.stride), k.stride);
@@ -223,18 +277,18 @@ __global__ __launch_bounds__(T) void collide_kernel(CollideK k, unsigned n_cells
       if (n & 1) {
         if (threadIdx.x == T - 1) {            // the triple, one pair after the other, each at half the variance
           const int p0 = A.perm[0], p1 = A.perm[1], p2 = A.perm[2];
-          count(collide_pair(k, A, p0, A, p1, k.a.f, k.a.f, fN, true, pair_draws(k, c0_a, 0u, lo_a + p0)));
-          count(collide_pair(k, A, p1, A, p2, k.a.f, k.a.f, fN, true, pair_draws(k, c0_a, 1u, lo_a + p1)));
-          count(collide_pair(k, A, p2, A, p0, k.a.f, k.a.f, fN, true, pair_draws(k, c0_a, 2u, lo_a + p2)));
+          count(pair_of<REL>(k, A, p0, A, p1, k.a.f, k.a.f, fN, true, pair_draws(k, c0_a, 0u, lo_a + p0)));
+          count(pair_of<REL>(k, A, p1, A, p2, k.a.f, k.a.f, fN, true, pair_draws(k, c0_a, 1u, lo_a + p1)));
+          count(pair_of<REL>(k, A, p2, A, p0, k.a.f, k.a.f, fN, true, pair_draws(k, c0_a, 2u, lo_a + p2)));
         }
         for (int m = threadIdx.x; m < (n - 3) / 2; m += T) {
           const int kf = A.perm[3 + 2 * m], ks = A.perm[4 + 2 * m];
-          count(collide_pair(k, A, kf, A, ks, k.a.f, k.a.f, fN, false, pair_draws(k, c0_a, (unsigned)(3 + m), lo_a + kf)));
+          count(pair_of<REL>(k, A, kf, A, ks, k.a.f, k.a.f, fN, false, pair_draws(k, c0_a, (unsigned)(3 + m), lo_a + kf)));
         }
       } else {
         for (int j = threadIdx.x; j < n / 2; j += T) {
           const int kf = A.perm[2 * j], ks = A.perm[2 * j + 1];
-          count(collide_pair(k, A, kf, A, ks, k.a.f, k.a.f, fN, false, pair_draws(k, c0_a, (unsigned)j, lo_a + kf)));
+          count(pair_of<REL>(k, A, kf, A, ks, k.a.f, k.a.f, fN, false, pair_draws(k, c0_a, (unsigned)j, lo_a + kf)));
         }
       }
     } else {
@@ -247,7 +301,7 @@ __global__ __launch_bounds__(T) void collide_kernel(CollideK k, unsigned n_cells
         const int ks = S.perm[m];
         for (int j = m; j < n_L; j += n_S) {     // this S particle's pairs, in ascending j
           const int kf = L.perm[j];
-          count(collide_pair(k, L, kf, S, ks, f_L, f_S, fN, false, pair_draws(k, c0_L, (unsigned)j, lo_L + kf)));
+          count(pair_of<REL>(k, L, kf, S, ks, f_L, f_S, fN, false, pair_draws(k, c0_L, (unsigned)j, lo_L + kf)));
         }
       }
     }
@@ -304,7 +358,18 @@ static int check_species(Engine *e, const CollideSpK &s, const CollideK &k, int 
   return 0;
 }
 
-int k_collide(Engine *e, const vpic_hip_collision_t &c, bool wants_tile_a, bool wants_tile_b) {
+template <bool REL>
+static void launch_collide(Engine *e, const CollideK &K, bool wave, bool same, unsigned groups, size_t lds, unsigned cells) {
+  if (wave) {
+    if (same) hipLaunchKernelGGL((collide_kernel<64, true, REL>), dim3(groups), dim3(64), lds, e->stream, K, cells);
+    else hipLaunchKernelGGL((collide_kernel<64, false, REL>), dim3(groups), dim3(64), lds, e->stream, K, cells);
+  } else {
+    if (same) hipLaunchKernelGGL((collide_kernel<256, true, REL>), dim3(groups), dim3(256), lds, e->stream, K, cells);
+    else hipLaunchKernelGGL((collide_kernel<256, false, REL>), dim3(groups), dim3(256), lds, e->stream, K, cells);
+  }
+}
+
+int k_collide(Engine *e, const vpic_hip_collision_t &c, bool wants_tile_a, bool wants_tile_b, bool relativistic) {
   for (auto &w : e->collide_last) w = 0;
   e->collide_instance = 0;
   if (!e->collide_dev) VH_CHECK(hipMalloc((void **)&e->collide_dev, COLLIDE_WORDS * sizeof(unsigned long long)));
@@ -315,7 +380,7 @@ int k_collide(Engine *e, const vpic_hip_collision_t &c, bool wants_tile_a, bool 
   const float m_ab = (c.m_a * m_b) / (c.m_a + m_b);
   const float V = (e->grid.dx * e->grid.dy) * e->grid.dz;
   CollideK K;
-  K.cvar = c.cvar; K.dt = c.dt; K.den = (V * m_ab) * m_ab;
+  K.cvar = c.cvar; K.dt = c.dt; K.den = relativistic ? V : (V * m_ab) * m_ab;
   K.seed = c.seed; K.call = c.call; K.rank = (unsigned)e->gk.rank;
   K.draws = e->collide_draws_n > 0 ? e->collide_draws : nullptr;
   K.words = e->collide_dev;
@@ -331,8 +396,8 @@ int k_collide(Engine *e, const vpic_hip_collision_t &c, bool wants_tile_a, bool 
     if (pl.sort_a) { if (sort_exact(e, A, wants_tile_a)) return 1; sorted = true; }
     if (pl.sort_b) { if (sort_exact(e, B, wants_tile_b)) return 1; sorted = true; }
     da = describe(A, K.tk); db = describe(B, K.tk);
-    K.a = species_k(A, da, c.sp_a, c.wq_a, m_ab / c.m_a);
-    K.b = species_k(B, db, c.sp_b, wq_b, m_ab / m_b);
+    K.a = species_k(A, da, c.sp_a, c.wq_a, relativistic ? c.m_a : m_ab / c.m_a);
+    K.b = species_k(B, db, c.sp_b, wq_b, relativistic ? m_b : m_ab / m_b);
     // (a species that is still not in a sorted order -- it holds nothing alive -- has no ranges to check)
     if (A.np > 0 && !da.tile_valid && !da.partition_valid) VH_FAIL("collide: species %d could not be sorted", c.sp_a);
     if (!same && B.np > 0 && !db.tile_valid && !db.partition_valid) VH_FAIL("collide: species %d could not be sorted", c.sp_b);
@@ -355,13 +420,8 @@ int k_collide(Engine *e, const vpic_hip_collision_t &c, bool wants_tile_a, bool 
   const size_t lds = sizeof(unsigned) * COLLIDE_SLAB_ARRAYS * (size_t)K.stride * (same ? 1 : 2);
   const unsigned cells = K.a.order == 2 ? (unsigned)(K.tk.ntiles * TILE_CELLS) : (unsigned)(K.nx * K.ny * K.nz);
   const unsigned groups = std::min(cells, (unsigned)(wave ? COLLIDE_MAX_GROUPS_WAVE : COLLIDE_MAX_GROUPS));
-  if (wave) {
-    if (same) hipLaunchKernelGGL((collide_kernel<64, true>), dim3(groups), dim3(64), lds, e->stream, K, cells);
-    else hipLaunchKernelGGL((collide_kernel<64, false>), dim3(groups), dim3(64), lds, e->stream, K, cells);
-  } else {
-    if (same) hipLaunchKernelGGL((collide_kernel<256, true>), dim3(groups), dim3(256), lds, e->stream, K, cells);
-    else hipLaunchKernelGGL((collide_kernel<256, false>), dim3(groups), dim3(256), lds, e->stream, K, cells);
-  }
+  if (relativistic) launch_collide<true>(e, K, wave, same, groups, lds, cells);
+  else launch_collide<false>(e, K, wave, same, groups, lds, cells);
   VH_CHECK(hipGetLastError());
   e->collide_instance = wave ? 1 : 2;
   VH_CHECK(hipMemcpyAsync(e->collide_host, e->collide_dev, COLLIDE_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));

@@ -495,8 +495,9 @@ constexpr int CELL_DIST_STATS = 8;       // words of Engine::cell_stats
 int k_cell_distribution(Engine *e, const vpic_hip_dist_t &d, const vpic_hip_dist_value_t *v, int n_val);   // cell_dist.hip: into Engine::cell_counts / cell_host, cell_sums / cell_sums_host; waits for the stream
 // select.hip: launches 1 and 2 (count_only: no masks), and launch 3 into Engine::sel_p / sel_f / sel_i where asked for; waits for the stream
 int k_species_select(Engine *e, Species &s, const vpic_hip_select_t &d, int64_t cap, bool want_p, bool want_f, bool want_i, bool count_only);
-// collide.hip: the checking pass, the sorts it asks for, the launch; wants_tile_a / _b: the order a sort of that species would produce now
-int k_collide(Engine *e, const vpic_hip_collision_t &c, bool wants_tile_a, bool wants_tile_b);
+// collide.hip: the checking pass, the sorts it asks for, the launch; wants_tile_a / _b: the order a sort of that species would produce now;
+// relativistic: the pair of vpic_hip_collide_relativistic
+int k_collide(Engine *e, const vpic_hip_collision_t &c, bool wants_tile_a, bool wants_tile_b, bool relativistic);
 int k_sort_p(Engine *e, Species &s, bool tile_order = false, bool may_fuse = false);   // may_fuse: the caller pushes the species next (see Species::fuse_pending)
 int k_sort_scan(Engine *e, const int *counts, int *starts, int n1);                  // exclusive scan of counts[0..n1) into starts[] and Engine::sort_next[]
 int k_sort_check(Engine *e, Species &s, const int *starts, int n1);                    // every cursor ended where the next key begins? (PW_SORT_CHECK; the next push fails loudly otherwise)

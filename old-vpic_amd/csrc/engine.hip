@@ -680,7 +680,8 @@ int vpic_hip_energy_p(vpic_hip_engine_t *e, int sp, double *energy) {
   return k_energy_p(e, e->species[sp], energy);
 }
 // Binary collisions (collide.hip).  The arguments are checked here, before anything is touched; the message names the argument.
-int vpic_hip_collide(vpic_hip_engine_t *e, const vpic_hip_collision_t *c) {
+// Both models take the same descriptor and the same checks; they differ in the pair alone.
+static int collide_checked(vpic_hip_engine_t *e, const vpic_hip_collision_t *c, bool relativistic) {
   ENGINE(e);
   if (!c) VH_FAIL("collide: NULL c");
   if (c->sp_a < 0 || (size_t)c->sp_a >= e->species.size()) VH_FAIL("collide: sp_a = %d is not a species", c->sp_a);
@@ -695,8 +696,10 @@ int vpic_hip_collide(vpic_hip_engine_t *e, const vpic_hip_collision_t *c) {
   const int64_t longest = std::max(e->species[c->sp_a].np, e->species[c->sp_b].np);
   if (e->collide_draws_n > 0 && e->collide_draws_n < longest)
     VH_FAIL("collide: the draws table holds %lld particles, the longer array %lld", (long long)e->collide_draws_n, (long long)longest);
-  return k_collide(e, *c, wants_tile_order(e, e->species[c->sp_a]), wants_tile_order(e, e->species[c->sp_b]));
+  return k_collide(e, *c, wants_tile_order(e, e->species[c->sp_a]), wants_tile_order(e, e->species[c->sp_b]), relativistic);
 }
+int vpic_hip_collide(vpic_hip_engine_t *e, const vpic_hip_collision_t *c) { return collide_checked(e, c, false); }
+int vpic_hip_collide_relativistic(vpic_hip_engine_t *e, const vpic_hip_collision_t *c) { return collide_checked(e, c, true); }
 int vpic_hip_collide_stats(vpic_hip_engine_t *e, int64_t out[6]) {
   ENGINE(e); if (!out) VH_FAIL("Bad output array");
   for (int k = 0; k < 6; k++) out[k] = e->collide_last[k];

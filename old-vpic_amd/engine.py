@@ -465,11 +465,13 @@ class Engine:
         return e.value
 
     # ---- binary Coulomb collisions (include/vpic_hip.h: vpic_hip_collide) ----
-    def collide(self, sp_a, sp_b=None, *, m_a, m_b=None, wq_a, wq_b=None, cvar, dt, seed, call):
+    def collide(self, sp_a, sp_b=None, *, m_a, m_b=None, wq_a, wq_b=None, cvar, dt, seed, call, relativistic=False):
         """Takizuka-Abe collisions of the particles of species sp_a among themselves (sp_b None or sp_a) or with those of
         sp_b, cell by cell on the device; only ux, uy, uz of the two species change.  m: mass of a physical particle, wq:
         1 / |charge of a physical particle| (a macro-particle weighs |q| * wq), cvar = (q_a q_b)^2 ln(Lambda) / (8 pi eps0^2
-        c^3), dt the time the call stands for, (seed, call) the counter of its random stream.  Non-relativistic (|u| << 1),
+        c^3), dt the time the call stands for, (seed, call) the counter of its random stream.  Non-relativistic (|u| << 1)
+        unless relativistic=True, which takes the pair of Perez et al. 2012 (vpic_hip_collide_relativistic: the same pairing,
+        draws and weight rule, the pair turned in its centre-of-momentum frame in double, sum m u and sum m gamma kept);
         rank-local, at most COLLIDE_MAX_CELL particles of a species per cell; a species whose cell ranges are not exact is
         sorted first (collide_stats()["sorted_first"]).  A copy of the species' particles held on the host is stale afterwards."""
         if sp_b is None:
@@ -478,7 +480,8 @@ class Engine:
         d = CollisionDesc(int(sp_a), int(sp_b), float(m_a), float(m_a if m_b is None and same else m_b if m_b is not None else -1.0),
                           float(wq_a), float(wq_a if wq_b is None and same else wq_b if wq_b is not None else -1.0),
                           float(cvar), float(dt), int(seed) & 0xffffffff, int(call) & 0xffffffff)
-        self._ck(self._l.vpic_hip_collide(self._h, C.byref(d)))
+        call_ = self._l.vpic_hip_collide_relativistic if relativistic else self._l.vpic_hip_collide
+        self._ck(call_(self._h, C.byref(d)))
 
     def collide_stats(self):
         """dict of the last collide call: cells with a pair, pairs scattered, pairs skipped (no relative velocity), pairs

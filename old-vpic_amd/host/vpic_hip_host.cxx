@@ -613,7 +613,7 @@ void vpic_simulation::collide(species_t *a, species_t *b, const collide_params_t
   c.wq_a = (float)(1.0 / fabs(prm.q_a)); c.wq_b = (float)(1.0 / fabs(a == b ? prm.q_a : prm.q_b));
   c.cvar = (float)prm.cvar; c.dt = (float)((double)prm.interval * (double)grid->dt);
   c.seed = prm.seed; c.call = (uint32_t)step;
-  CK(vpic_hip_collide(engine, &c));
+  CK(prm.relativistic ? vpic_hip_collide_relativistic(engine, &c) : vpic_hip_collide(engine, &c));
   // both species lie sorted by cell now (they did, or the call sorted them): a sort that was due this step has been made
   if ((size_t)ia < sort_pending.size()) sort_pending[(size_t)ia] = 0;
   if ((size_t)ib < sort_pending.size()) sort_pending[(size_t)ib] = 0;

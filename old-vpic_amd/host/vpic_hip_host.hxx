@@ -356,7 +356,7 @@ public:
   int64_t select_particles(species_t *sp, const vpic_hip_select_t *s, int64_t cap, particle_t *p, float *fields, int64_t *index);
   // Binary Coulomb collisions (Takizuka & Abe) of the particles of species a among themselves (b NULL or a) or with those of
   // b, cell by cell on the device (vpic_hip_collide, include/vpic_hip.h: the model, the pairing, the arithmetic, the limits --
-  // non-relativistic, rank-local, at most VPIC_HIP_COLLIDE_MAX_CELL particles of a species per cell).  For
+  // non-relativistic unless prm.relativistic, rank-local, at most VPIC_HIP_COLLIDE_MAX_CELL particles of a species per cell).  For
   // begin_particle_collisions: the call does its work on the steps that are multiples of prm.interval and returns at once
   // on the others; the host derives wq = 1 / |charge|, dt = interval * grid->dt and the stream's call counter = step.  What
   // a hook has written to sp->p before the call reaches the device first; afterwards the particle mirrors are stale like
@@ -368,6 +368,7 @@ public:
     double cvar;              // (q_a q_b)^2 ln(Lambda) / (8 pi eps0^2 c^3) in the deck's units
     int interval;             // collide every `interval` steps, for the time interval * dt
     unsigned seed;
+    int relativistic;         // 0: vpic_hip_collide (|u| << 1); non-zero: vpic_hip_collide_relativistic (hot plasmas; include/vpic_hip.h gives the range of |u|).  An initialiser of seven values leaves it 0
   };
   void collide(species_t *a, species_t *b, const collide_params_t &prm);
   int64_t particle_mirror_downloads(void) const;    // whole-species downloads into the host mirrors so far (diagnostics, tests)
