@@ -33,7 +33,7 @@ __device__ __forceinline__ unsigned c_mix32(unsigned x) { x ^= x >> 16; x *= 0x7
 __device__ __forceinline__ float c_unit(unsigned r) { return ((float)(r >> 8) + 0.5f) * (1.f / 16777216.f); }
 
 struct CollideSpK {
-  float *ux, *uy, *uz; const float *q; const int *i; const int *starts;
+  float *ux, *uy, *uz; const float *q; const float4 *r; const int *starts;
   int order, np;                     // order: 0 nothing to pair, 1 starts = partition[voxel], 2 starts = tpart[tile key]
   float wq, f;                       // f = m_ab / m of this species (the relativistic model: m itself)
   unsigned id;
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) void collide_check_particles(CollideSpK s, Col
   const int p = blockIdx.x * 256 + threadIdx.x;
   bool bad = false;
   if (p < s.np) {
-    const int v = s.i[p];
+    const int v = record_cell(s.r, p);
     if (v < 0 || v >= k.nv) bad = true;                       // a dead slot, or no voxel at all
     else {
       int cx, cy, cz;
@@ -333,7 +333,7 @@ static CollideSpecies describe(const Species &s, const TileK &tk) {
 }
 static CollideSpK species_k(const Species &s, const CollideSpecies &d, int id, float wq, float f) {
   CollideSpK k;
-  k.ux = s.p.ux; k.uy = s.p.uy; k.uz = s.p.uz; k.q = s.p.q; k.i = s.p.i;
+  k.ux = s.p.ux; k.uy = s.p.uy; k.uz = s.p.uz; k.q = s.p.q; k.r = s.p.r;
   k.order = s.np == 0 ? 0 : d.tile_valid ? 2 : 1;
   k.starts = k.order == 2 ? s.tpart : s.partition;
   k.np = (int)s.np; k.wq = wq; k.f = f; k.id = (unsigned)id;

@@ -61,10 +61,8 @@ __device__ __forceinline__ DistRaw dist_load(const ParticlesK &p, long long idx,
   DistRaw r{-1, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const bool u = FIELDS && (need & NEED_FIELD_U);
   if (idx < end) {
-    r.voxel = p.i[idx];
-    if (FIELDS || (need & 1u)) r.dx = p.dx[idx];
-    if (FIELDS || (need & 2u)) r.dy = p.dy[idx];
-    if (FIELDS || (need & 4u)) r.dz = p.dz[idx];
+    const float4 rec = p.r[idx];                          // (position and cell are one 16-byte record: engine.h)
+    r.voxel = record_cell(rec); r.dx = rec.x; r.dy = rec.y; r.dz = rec.z;
     if (u || (need & (NEED_KE | 1u << VPIC_HIP_COORD_UX))) r.ux = p.ux[idx];
     if (u || (need & (NEED_KE | 1u << VPIC_HIP_COORD_UY))) r.uy = p.uy[idx];
     if (u || (need & (NEED_KE | 1u << VPIC_HIP_COORD_UZ))) r.uz = p.uz[idx];

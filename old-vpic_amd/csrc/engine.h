@@ -41,12 +41,27 @@ struct FieldsK {
   uint16_t *m[M_NCOMP];   // material ids; all null when the table holds a single material
 };
 
-// Particles of one species, struct-of-arrays, kept (approximately) cell-sorted.
+// Particles of one species, kept (approximately) cell-sorted: one array of 16-byte POSITION RECORDS {dx, dy, dz, i} -- the
+// cell as the bit pattern of the fourth float, as WaveQueue::pos_i (push.hip) carries it -- and the four 4-byte arrays
+// ux, uy, uz, q.  Position and cell travel together wherever they change together: a cell-crosser's final state is one
+// 16-byte store.  32 bytes per particle, as the vpic_particle_t of the C ABI: its first 16 bytes are this record.
 struct ParticlesK {
-  float *dx, *dy, *dz;
-  int *i;
+  float4 *r;
   float *ux, *uy, *uz, *q;
 };
+__host__ __device__ __forceinline__ float4 make_record(float dx, float dy, float dz, int i) {
+  union { int i; float f; } w; w.i = i;
+  return make_float4(dx, dy, dz, w.f);
+}
+// the cell word alone (kernels that need only keys, or only whether a slot is dead: i < 0): a 4-byte access at a 16-byte stride
+__device__ __forceinline__ int record_cell(const float4 *r, long long k) { return __float_as_int(r[k].w); }
+__device__ __forceinline__ int record_cell(const float4 &v) { return __float_as_int(v.w); }
+__device__ __forceinline__ void record_set_cell(float4 *r, long long k, int i) { r[k].w = __int_as_float(i); }
+__host__ __device__ __forceinline__ ParticlesK offset_particles(const ParticlesK &p, int64_t at) {
+  ParticlesK o = p;
+  o.r += at; o.ux += at; o.uy += at; o.uz += at; o.q += at;
+  return o;
+}
 
 // What the cell-crossing path of advance_p needs and the push loop does not (push.hip); one
 // record per species in device memory, written when the species is created.
@@ -419,6 +434,7 @@ void host_will_write(void *p, size_t bytes);
 constexpr int PUSH_TILE = 64;          // particles per wavefront pass of the push kernel (push.hip)
 constexpr int64_t PARTICLE_PAD = 2048;   // allocation granularity of the particle arrays (every kernel guards its accesses by np)
 int alloc_particles(ParticlesK &p, int64_t n);
+void free_particles(ParticlesK &p);
 
 // kernels (one translation unit each)
 int k_fields_from_aos(Engine *e, const vpic_field_t *host);

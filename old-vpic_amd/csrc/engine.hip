@@ -167,8 +167,8 @@ int acc_finalize(Engine *e) {
   return 0;
 }
 
-static void free_particles(ParticlesK &p) {
-  (void)hipFree(p.dx); (void)hipFree(p.dy); (void)hipFree(p.dz); (void)hipFree(p.i);
+void free_particles(ParticlesK &p) {
+  (void)hipFree(p.r);
   (void)hipFree(p.ux); (void)hipFree(p.uy); (void)hipFree(p.uz); (void)hipFree(p.q);
   p = ParticlesK{};
 }

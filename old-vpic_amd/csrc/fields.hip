@@ -930,10 +930,12 @@ int k_clear_rhof(Engine *e) {
 __global__ __launch_bounds__(256)
 void accumulate_rho_p_kernel(float *__restrict__ rhof, ParticlesK p, int np, float r8V, int sy, int sz) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= np || p.i[idx] < 0) return;          // (a dead slot: engine.h, Species::n_holes)
+  if (idx >= np) return;
+  const float4 rec = p.r[idx];
+  if (record_cell(rec) < 0) return;               // (a dead slot: engine.h, Species::n_holes)
   float w[8];
-  node_weights(p.dx[idx], p.dy[idx], p.dz[idx], p.q[idx], r8V, w);
-  float *r = rhof + p.i[idx];
+  node_weights(rec.x, rec.y, rec.z, p.q[idx], r8V, w);
+  float *r = rhof + record_cell(rec);
   atomicAdd(r, w[0]); atomicAdd(r + 1, w[1]); atomicAdd(r + sy, w[2]); atomicAdd(r + sy + 1, w[3]);
   atomicAdd(r + sz, w[4]); atomicAdd(r + sz + 1, w[5]); atomicAdd(r + sz + sy, w[6]); atomicAdd(r + sz + sy + 1, w[7]);
 }
@@ -950,7 +952,8 @@ void accumulate_rho_cells_kernel(float *__restrict__ rhof, ParticlesK p, const i
 #pragma unroll 1
   for (int idx = first; idx < last; idx++) {
     float w[8];
-    node_weights(p.dx[idx], p.dy[idx], p.dz[idx], p.q[idx], r8V, w);
+    const float4 rec = p.r[idx];
+    node_weights(rec.x, rec.y, rec.z, p.q[idx], r8V, w);
     s0 += w[0]; s1 += w[1]; s2 += w[2]; s3 += w[3]; s4 += w[4]; s5 += w[5]; s6 += w[6]; s7 += w[7];
   }
   float *r = rhof + v;

@@ -79,14 +79,15 @@ struct MomCount { unsigned live = 0, lds = 0, global = 0, range = 0; };
 // is counted and adds; any other returns before a contribution is formed.
 template <int NM, typename ACC, bool WINDOW, int SEL>
 __device__ __forceinline__ void moments_of_particle(const MomKS<SEL> &K, ACC *__restrict__ out, ACC *s_win, long long idx, int bx, int by, int bz, MomCount &n) {
-  const int voxel = K.p.i[idx];
+  const float4 rec = K.p.r[idx];
+  const int voxel = record_cell(rec);
   if (voxel < 0 || voxel >= K.nv_safe) return;            // i < 0: a dead slot (engine.h, Species::n_holes)
   HydroP P;
   if constexpr (SEL != MOM_SEL_NONE) {
     static_assert(NM == HYDRO_MOMENTS, "a selection is for the hydro moments");
     constexpr bool FIELDS = SEL == MOM_SEL_FIELD;
     if (K.sel.use_tag && !select_tag_ok(K.sel.s, K.tag ? K.tag[idx] : 0)) return;          // (uniform: the tags are read when a flag is set)
-    const DistRaw r{voxel, K.p.dx[idx], K.p.dy[idx], K.p.dz[idx], K.p.ux[idx], K.p.uy[idx], K.p.uz[idx]};
+    const DistRaw r{voxel, rec.x, rec.y, rec.z, K.p.ux[idx], K.p.uy[idx], K.p.uz[idx]};
     InterpK f;
     if (FIELDS) f = load_interp(K.fi, voxel);
     if (K.sel.s.n_sel > 0) {
@@ -101,9 +102,9 @@ __device__ __forceinline__ void moments_of_particle(const MomKS<SEL> &K, ACC *__
   } else {
     n.live++;
     if constexpr (NM == HYDRO_MOMENTS)
-      hydro_particle(K.p.dx[idx], K.p.dy[idx], K.p.dz[idx], K.p.ux[idx], K.p.uy[idx], K.p.uz[idx], K.p.q[idx], load_interp(K.fi, voxel), K.h, P);
+      hydro_particle(rec.x, rec.y, rec.z, K.p.ux[idx], K.p.uy[idx], K.p.uz[idx], K.p.q[idx], load_interp(K.fi, voxel), K.h, P);
     else
-      node_weights(K.p.dx[idx], K.p.dy[idx], K.p.dz[idx], K.p.q[idx], K.h.r8V, P.w);
+      node_weights(rec.x, rec.y, rec.z, K.p.q[idx], K.h.r8V, P.w);
   }
   bool inside = false;
   int slot0 = 0;

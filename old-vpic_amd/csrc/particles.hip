@@ -23,7 +23,7 @@ __global__ void particles_from_aos_kernel(ParticlesK p, int64_t *tag, int64_t *t
   if (t >= n) return;
   const vpic_particle_t s = src[t];
   const int64_t k = first + t;
-  p.dx[k] = s.dx; p.dy[k] = s.dy; p.dz[k] = s.dz; p.i[k] = s.i;
+  p.r[k] = make_record(s.dx, s.dy, s.dz, s.i);           // (the first 16 bytes of a vpic_particle_t, as they stand)
   p.ux[k] = s.ux; p.uy[k] = s.uy; p.uz[k] = s.uz; p.q[k] = s.q;
   if (tag) { tag[k] = s.tag; tag2[k] = s.tag2; }
 }
@@ -33,7 +33,8 @@ __global__ void particles_to_aos_kernel(ParticlesK p, const int64_t *tag, const 
   if (t >= n) return;
   const int64_t k = first + t;
   vpic_particle_t s;
-  s.dx = p.dx[k]; s.dy = p.dy[k]; s.dz = p.dz[k]; s.i = p.i[k];
+  const float4 rec = p.r[k];
+  s.dx = rec.x; s.dy = rec.y; s.dz = rec.z; s.i = record_cell(rec);
   s.ux = p.ux[k]; s.uy = p.uy[k]; s.uz = p.uz[k]; s.q = p.q[k];
   s.tag = tag ? tag[k] : 0; s.tag2 = tag ? tag2[k] : 0;
   dst[t] = s;
@@ -123,10 +124,8 @@ void load_maxwellian_kernel(ParticlesK p, GridK g, int ppc, int np, unsigned see
   if (idx >= np) return;
   const int cell = idx / ppc;
   const int cz = cell / (g.nx * g.ny), r = cell - cz * g.nx * g.ny, cy = r / g.nx, cx = r - cy * g.nx;
-  p.i[idx] = (cx + 1) + g.sy * (cy + 1) + g.sz * (cz + 1);
-  p.dx[idx] = 2.f * u01(seed, idx, 0) - 1.f;
-  p.dy[idx] = 2.f * u01(seed, idx, 1) - 1.f;
-  p.dz[idx] = 2.f * u01(seed, idx, 2) - 1.f;
+  p.r[idx] = make_record(2.f * u01(seed, idx, 0) - 1.f, 2.f * u01(seed, idx, 1) - 1.f, 2.f * u01(seed, idx, 2) - 1.f,
+                         (cx + 1) + g.sy * (cy + 1) + g.sz * (cz + 1));
   const float r1 = sqrtf(-2.f * logf(u01(seed, idx, 3))), a1 = 6.2831853f * u01(seed, idx, 4);
   const float r2 = sqrtf(-2.f * logf(u01(seed, idx, 5))), a2 = 6.2831853f * u01(seed, idx, 6);
   p.ux[idx] = ux0 + vth * r1 * cosf(a1);
@@ -184,10 +183,10 @@ TileK make_tile_k(const GridK &g) {
 
 template <bool TILE>
 __global__ __launch_bounds__(256)
-void sort_count_kernel(const int *__restrict__ cell, int np, int *__restrict__ count, const TileK t) {
+void sort_count_kernel(const float4 *__restrict__ rec, int np, int *__restrict__ count, const TileK t) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63;
-  const int key = idx < np ? cell[idx] : -1;
+  const int key = idx < np ? record_cell(rec, idx) : -1;   // (the keys alone, at a 16-byte stride)
   const bool valid = key >= 0;                            // (a dead slot -- engine.h, Species::n_holes -- is not counted: the sort drops it)
   int leader, rank, cnt;
   group_info(key, valid, lane, leader, rank, cnt);
@@ -253,11 +252,11 @@ void sort_scatter_kernel(ParticlesK in, ParticlesK out, const int64_t *tin, cons
                          int64_t *tout, int64_t *t2out, int np, int *__restrict__ next, const TileK t) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63;
-  const int key = idx < np ? in.i[idx] : -1;
+  const int li = idx < np ? idx : 0;
+  const float4 rec = in.r[li];
+  const int key = idx < np ? record_cell(rec) : -1;
   const bool valid = key >= 0;
   // issue the particle loads before the slot reservation so that both round trips overlap
-  const int li = idx < np ? idx : 0;
-  const float dx = in.dx[li], dy = in.dy[li], dz = in.dz[li];
   const float ux = in.ux[li], uy = in.uy[li], uz = in.uz[li], q = in.q[li];
   int leader, rank, cnt;
   group_info(key, valid, lane, leader, rank, cnt);
@@ -266,7 +265,7 @@ void sort_scatter_kernel(ParticlesK in, ParticlesK out, const int64_t *tin, cons
   base = __shfl(base, leader);
   if (!valid) return;
   const int dst = base + rank;
-  out.dx[dst] = dx; out.dy[dst] = dy; out.dz[dst] = dz; out.i[dst] = key;
+  out.r[dst] = rec;
   out.ux[dst] = ux; out.uy[dst] = uy; out.uz[dst] = uz; out.q[dst] = q;
   if (tin) { tout[dst] = tin[idx]; t2out[dst] = t2in[idx]; }
 }
@@ -276,7 +275,7 @@ void sort_scatter_kernel(ParticlesK in, ParticlesK out, const int64_t *tin, cons
 // fragments of a few particles (0.37 of the roofline).  A workgroup's 2048 consecutive particles hold some 50-150 distinct
 // keys a few steps after a sort: they are counted in an LDS hash table (key -> count), ONE global atomic per distinct key per
 // workgroup counts / reserves, and the scatter moves each of the eight arrays through an 8 KB LDS buffer in destination order,
-// so that what goes to one key leaves as one contiguous run.  Same result as the kernels above (partition[] / tpart[]
+// so that what goes to one key leaves as one contiguous run (today five arrays: the position records and ux, uy, uz, q).  Same result as the kernels above (partition[] / tpart[]
 // identical; the order within a key is the atomics' order, as before).
 #ifndef VPIC_HIP_SORT_THREADS
 #define VPIC_HIP_SORT_THREADS 256
@@ -304,14 +303,14 @@ __device__ __forceinline__ int wg_slot(int *s_key, int skey) {
 
 template <bool TILE>
 __global__ __launch_bounds__(WG_T)
-void wg_count_kernel(const int *__restrict__ cell, int np, int *__restrict__ count, const TileK t) {
+void wg_count_kernel(const float4 *__restrict__ rec, int np, int *__restrict__ count, const TileK t) {
   __shared__ int s_key[WG_TABLE], s_cnt[WG_TABLE];
   for (int k = threadIdx.x; k < WG_TABLE; k += WG_T) { s_key[k] = -1; s_cnt[k] = 0; }
   __syncthreads();
   const int first = blockIdx.x * WG_CHUNK;
   int key[WG_PER_THREAD];
 #pragma unroll
-  for (int j = 0; j < WG_PER_THREAD; j++) { const int idx = first + j * WG_T + threadIdx.x; key[j] = idx < np ? cell[idx] : -1; }
+  for (int j = 0; j < WG_PER_THREAD; j++) { const int idx = first + j * WG_T + threadIdx.x; key[j] = idx < np ? record_cell(rec, idx) : -1; }
   const int lane = threadIdx.x & 63;
 #pragma unroll
   for (int j = 0; j < WG_PER_THREAD; j++) {
@@ -336,11 +335,14 @@ template <bool TILE, bool COARSE = false>
 __global__ __launch_bounds__(WG_T)
 void wg_scatter_kernel(ParticlesK in, ParticlesK out, const int64_t *tin, const int64_t *t2in,
                        int64_t *tout, int64_t *t2out, int np, int *__restrict__ next, const TileK t) {
-  // (the four tables are dead once every particle knows its place: their 8 KB then serve as the second staging buffer)
-  __shared__ int s_tables[WG_CHUNK > 4 * WG_TABLE ? WG_CHUNK : 4 * WG_TABLE];
+  // (the four tables are dead once every particle knows its place: their 8 KB then serve as the second staging buffer; the two
+  // buffers lie side by side, 16 KB that hold half a chunk of position records)
+  static_assert(WG_CHUNK >= 4 * WG_TABLE, "the tables fit the first staging buffer");
+  __shared__ float4 s_both[WG_CHUNK / 2];
+  int *const s_tables = reinterpret_cast<int *>(s_both);
+  float *const s_stage = reinterpret_cast<float *>(s_both) + WG_CHUNK;
   int *const s_key = s_tables, *const s_cnt = s_tables + WG_TABLE, *const s_lbase = s_tables + 2 * WG_TABLE, *const s_gbase = s_tables + 3 * WG_TABLE;
   __shared__ int s_dst[WG_CHUNK];
-  __shared__ float s_stage[WG_CHUNK];
   __shared__ int s_wave[WG_T / 64], s_total;
   for (int k = threadIdx.x; k < WG_TABLE; k += WG_T) { s_key[k] = -1; s_cnt[k] = 0; }
   __syncthreads();
@@ -353,7 +355,7 @@ void wg_scatter_kernel(ParticlesK in, ParticlesK out, const int64_t *tin, const 
 #endif
   int slot[WG_PER_THREAD], rank[WG_PER_THREAD], key[WG_PER_THREAD];
 #pragma unroll
-  for (int j = 0; j < WG_PER_THREAD; j++) { const int idx = first + j * WG_T + threadIdx.x; key[j] = idx < np ? in.i[idx] : -1; }
+  for (int j = 0; j < WG_PER_THREAD; j++) { const int idx = first + j * WG_T + threadIdx.x; key[j] = idx < np ? record_cell(in.r, idx) : -1; }
   const int lane = threadIdx.x & 63;
 #pragma unroll
   for (int j = 0; j < WG_PER_THREAD; j++) {
@@ -400,20 +402,50 @@ void wg_scatter_kernel(ParticlesK in, ParticlesK out, const int64_t *tin, const 
   }
   __syncthreads();
   const int n_staged = s_total;
-  // one array at a time through a staging buffer: read in array order, written in destination order.  Two buffers take
-  // turns and the next array's loads are issued before this one's stores: one barrier per array, and the loads' round trip
-  // runs behind the stores instead of in front of them.
-  float *const src[8] = {in.dx, in.dy, in.dz, reinterpret_cast<float *>(in.i), in.ux, in.uy, in.uz, in.q};
-  float *const dst[8] = {out.dx, out.dy, out.dz, reinterpret_cast<float *>(out.i), out.ux, out.uy, out.uz, out.q};
+  // one array at a time through a staging buffer: read in array order, written in destination order.
+  // First the position records, 16 bytes each: the two buffers together hold half a chunk of them, so the records go through
+  // in two halves of the staging order (the LDS stays at 24 KB, six workgroups per CU), each leaving as whole records.
+  float *const src[4] = {in.ux, in.uy, in.uz, in.q};
+  float *const dst[4] = {out.ux, out.uy, out.uz, out.q};
   float *const stage2 = reinterpret_cast<float *>(s_tables);
   float v[WG_PER_THREAD];
+  {
+    constexpr int HALF = WG_CHUNK / 2, GROUP = 4;        // (records in registers at a time: eight would cost the sixth workgroup per CU)
 #pragma unroll
-  for (int j = 0; j < WG_PER_THREAD; j++) { const int idx = first + j * WG_T + threadIdx.x; v[j] = (slot[j] != -2) ? src[0][idx] : 0.f; }
+    for (int half = 0; half < 2; half++) {
 #pragma unroll
-  for (int f = 0; f < 8; f++) {                                        // (unrolled: the array pointers stay in scalar registers)
+      for (int j0 = 0; j0 < WG_PER_THREAD; j0 += GROUP) {
+        float4 rec[GROUP];
+        bool here[GROUP];                                  // this half takes the particle: each record is read once
+#pragma unroll
+        for (int j = 0; j < GROUP; j++) {
+          const int idx = first + (j0 + j) * WG_T + threadIdx.x;
+          here[j] = local[j0 + j] >= 0 ? (local[j0 + j] >= HALF) == (half == 1) : (slot[j0 + j] == -1 && half == 0);
+          rec[j] = here[j] ? in.r[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int j = 0; j < GROUP; j++) {
+          if (!here[j]) continue;
+          if (local[j0 + j] >= 0) s_both[local[j0 + j] - half * HALF] = rec[j];
+          else out.r[rank[j0 + j]] = rec[j];               // (table overflow: straight to its place)
+        }
+      }
+      if (half == 1) {                                     // (the first 4-byte array's loads run behind the records' last stores)
+#pragma unroll
+        for (int j = 0; j < WG_PER_THREAD; j++) { const int idx = first + j * WG_T + threadIdx.x; v[j] = (slot[j] != -2) ? src[0][idx] : 0.f; }
+      }
+      __syncthreads();
+      for (int k = threadIdx.x; k < HALF; k += WG_T) { if (half * HALF + k < n_staged) out.r[s_dst[half * HALF + k]] = s_both[k]; }
+      __syncthreads();                                     // (both buffers are written again at once)
+    }
+  }
+  // Then the four 4-byte arrays: the two buffers take turns and the next array's loads are issued before this one's stores --
+  // one barrier per array, and the loads' round trip runs behind the stores instead of in front of them.
+#pragma unroll
+  for (int f = 0; f < 4; f++) {                                        // (unrolled: the array pointers stay in scalar registers)
     float *const stage = (f & 1) ? stage2 : s_stage;
     float vn[WG_PER_THREAD];
-    if (f + 1 < 8) {
+    if (f + 1 < 4) {
 #pragma unroll
       for (int j = 0; j < WG_PER_THREAD; j++) { const int idx = first + j * WG_T + threadIdx.x; vn[j] = (slot[j] != -2) ? src[f + 1][idx] : 0.f; }
     }
@@ -425,7 +457,7 @@ void wg_scatter_kernel(ParticlesK in, ParticlesK out, const int64_t *tin, const 
     __syncthreads();                                                   // (the buffer is written again two arrays on, behind the next barrier)
 #pragma unroll
     for (int j = 0; j < WG_PER_THREAD; j++) { const int k = j * WG_T + threadIdx.x; if (k < n_staged) dst[f][s_dst[k]] = stage[k]; }
-    if (f + 1 < 8) {
+    if (f + 1 < 4) {
 #pragma unroll
       for (int j = 0; j < WG_PER_THREAD; j++) v[j] = vn[j];
     }
@@ -466,7 +498,7 @@ __device__ __forceinline__ int coarse_slot(int *s_key, int tile) {
 }
 
 __global__ __launch_bounds__(256)
-void coarse_count_kernel(const int *__restrict__ cell, int np, int *__restrict__ count, const TileK t) {
+void coarse_count_kernel(const float4 *__restrict__ rec, int np, int *__restrict__ count, const TileK t) {
   __shared__ int s_key[COARSE_TABLE], s_cnt[COARSE_TABLE];
   if (threadIdx.x < COARSE_TABLE) { s_key[threadIdx.x] = -1; s_cnt[threadIdx.x] = 0; }
   __syncthreads();
@@ -474,8 +506,9 @@ void coarse_count_kernel(const int *__restrict__ cell, int np, int *__restrict__
 #pragma unroll
   for (int j = 0; j < COARSE_PER_THREAD; j++) {
     const int idx = first + j * 256 + threadIdx.x;
-    if (idx < np && cell[idx] >= 0) {
-      const int tile = tile_of(cell[idx], t);
+    const int voxel = idx < np ? record_cell(rec, idx) : -1;
+    if (voxel >= 0) {
+      const int tile = tile_of(voxel, t);
       const int h = coarse_slot(s_key, tile);
       if (h >= 0) atomicAdd(&s_cnt[h], 1);
       else atomicAdd(&count[tile * TILE_CELLS], 1);                  // table full (cannot happen with sane input)
@@ -490,7 +523,8 @@ void coarse_count_kernel(const int *__restrict__ cell, int np, int *__restrict__
 int alloc_particles(ParticlesK &p, int64_t n_req) {
   const int64_t n = (n_req + PUSH_TILE + PARTICLE_PAD - 1) / PARTICLE_PAD * PARTICLE_PAD;
   if (alloc_particles_raw(p, n)) return 1;
-  float *arr[8] = {p.dx, p.dy, p.dz, reinterpret_cast<float *>(p.i), p.ux, p.uy, p.uz, p.q};
+  VH_CHECK(hipMemset(p.r + (n - PARTICLE_PAD), 0, sizeof(float4) * PARTICLE_PAD));
+  float *arr[4] = {p.ux, p.uy, p.uz, p.q};
   for (float *a : arr) VH_CHECK(hipMemset(a + (n - PARTICLE_PAD), 0, sizeof(float) * PARTICLE_PAD));
   // The fills run on the null stream, which does not order itself against the engine's (non-blocking) stream: without this
   // wait the first sort into a fresh array could be overtaken by them -- and for a species of fewer than 2048 particles
@@ -498,12 +532,11 @@ int alloc_particles(ParticlesK &p, int64_t n_req) {
   VH_CHECK(hipDeviceSynchronize());
   return 0;
 }
-// (Eight allocations, not one block: tried in round 3 for the sake of base + k * stride addressing in kernels short of scalar
-// registers -- one physically contiguous block costs the push 7 % at 256^3 x 64 ppc and 20 % on the 512-ppc drift deck, with or
-// without a skewed stride; the driver's placement of separate allocations spreads the eight streams better than any stride tried.)
+// (Separate allocations, not one block -- hipMalloc aligns each to far more than a record's 16 bytes.  One block was tried in
+// round 3, with eight 4-byte arrays, for the sake of base + k * stride addressing in kernels short of scalar registers: one physically contiguous block costs the push 7 % at 256^3 x 64 ppc and 20 % on the 512-ppc drift deck, with or
+// without a skewed stride; the driver's placement of separate allocations spreads the streams better than any stride tried.)
 static int alloc_particles_raw_impl(ParticlesK &p, int64_t n) {
-  VH_CHECK(hipMalloc(&p.dx, sizeof(float) * n)); VH_CHECK(hipMalloc(&p.dy, sizeof(float) * n));
-  VH_CHECK(hipMalloc(&p.dz, sizeof(float) * n)); VH_CHECK(hipMalloc(&p.i, sizeof(int) * n));
+  VH_CHECK(hipMalloc(&p.r, sizeof(float4) * n));
   VH_CHECK(hipMalloc(&p.ux, sizeof(float) * n)); VH_CHECK(hipMalloc(&p.uy, sizeof(float) * n));
   VH_CHECK(hipMalloc(&p.uz, sizeof(float) * n)); VH_CHECK(hipMalloc(&p.q, sizeof(float) * n));
   return 0;
@@ -546,7 +579,7 @@ int k_sort_p(Engine *e, Species &s, bool tile_order, bool may_fuse) {
   s.tile_valid = false;
   if (s.np == s.n_holes) { s.np = 0; s.n_holes = 0; }                         // nothing alive
   if (s.np == 0) return 0;                                                     // sort_p.c:35
-  if (!s.aux.dx && alloc_particles(s.aux, s.max_np)) return 1;
+  if (!s.aux.r && alloc_particles(s.aux, s.max_np)) return 1;
   if (s.has_tags && !s.tag_aux) {
     VH_CHECK(hipMalloc(&s.tag_aux, sizeof(int64_t) * s.max_np));
     VH_CHECK(hipMalloc(&s.tag2_aux, sizeof(int64_t) * s.max_np));
@@ -573,13 +606,13 @@ int k_sort_p(Engine *e, Species &s, bool tile_order, bool may_fuse) {
   if (counted) {}
   else VH_CHECK(hipMemsetAsync(e->sort_next, 0, sizeof(int) * n1, e->stream));
   if (counted) {}
-  else if (coarse) hipLaunchKernelGGL(coarse_count_kernel, dim3((np + COARSE_CHUNK - 1) / COARSE_CHUNK), dim3(256), 0, e->stream, s.p.i, np, e->sort_next, tk);
+  else if (coarse) hipLaunchKernelGGL(coarse_count_kernel, dim3((np + COARSE_CHUNK - 1) / COARSE_CHUNK), dim3(256), 0, e->stream, (const float4 *)s.p.r, np, e->sort_next, tk);
   else if (count_by_wave) {
-    if (tile_order) hipLaunchKernelGGL(sort_count_kernel<true>, dim3((np + 255) / 256), dim3(256), 0, e->stream, s.p.i, np, e->sort_next, tk);
-    else hipLaunchKernelGGL(sort_count_kernel<false>, dim3((np + 255) / 256), dim3(256), 0, e->stream, s.p.i, np, e->sort_next, tk);
+    if (tile_order) hipLaunchKernelGGL(sort_count_kernel<true>, dim3((np + 255) / 256), dim3(256), 0, e->stream, (const float4 *)s.p.r, np, e->sort_next, tk);
+    else hipLaunchKernelGGL(sort_count_kernel<false>, dim3((np + 255) / 256), dim3(256), 0, e->stream, (const float4 *)s.p.r, np, e->sort_next, tk);
   }
-  else if (tile_order) hipLaunchKernelGGL(wg_count_kernel<true>, dim3((np + WG_CHUNK - 1) / WG_CHUNK), dim3(WG_T), 0, e->stream, s.p.i, np, e->sort_next, tk);
-  else hipLaunchKernelGGL(wg_count_kernel<false>, dim3((np + WG_CHUNK - 1) / WG_CHUNK), dim3(WG_T), 0, e->stream, s.p.i, np, e->sort_next, tk);
+  else if (tile_order) hipLaunchKernelGGL(wg_count_kernel<true>, dim3((np + WG_CHUNK - 1) / WG_CHUNK), dim3(WG_T), 0, e->stream, (const float4 *)s.p.r, np, e->sort_next, tk);
+  else hipLaunchKernelGGL(wg_count_kernel<false>, dim3((np + WG_CHUNK - 1) / WG_CHUNK), dim3(WG_T), 0, e->stream, (const float4 *)s.p.r, np, e->sort_next, tk);
   if (k_sort_scan(e, counts, starts, n1)) return 1;
   if (coarse) hipLaunchKernelGGL((wg_scatter_kernel<true, true>), dim3(((np + WG_CHUNK - 1) / WG_CHUNK + 7) / 8 * 8), dim3(WG_T), 0, e->stream, s.p, s.aux,
                              s.has_tags ? s.tag : nullptr, s.tag2, s.tag_aux, s.tag2_aux, np, e->sort_next, tk);
@@ -639,19 +672,16 @@ int k_species_reserve(Engine *e, Species &s, int64_t max_np, int64_t max_nm) {
   if (max_np > s.max_np) {
     ParticlesK bigger{};
     if (alloc_particles(bigger, max_np)) return 1;
-    float *src[8] = {s.p.dx, s.p.dy, s.p.dz, reinterpret_cast<float *>(s.p.i), s.p.ux, s.p.uy, s.p.uz, s.p.q};
-    float *dst[8] = {bigger.dx, bigger.dy, bigger.dz, reinterpret_cast<float *>(bigger.i), bigger.ux, bigger.uy, bigger.uz, bigger.q};
-    for (int a = 0; a < 8; a++) {
+    float *src[4] = {s.p.ux, s.p.uy, s.p.uz, s.p.q};
+    float *dst[4] = {bigger.ux, bigger.uy, bigger.uz, bigger.q};
+    if (s.np > 0) VH_CHECK(hipMemcpyAsync(bigger.r, s.p.r, sizeof(float4) * (size_t)s.np, hipMemcpyDeviceToDevice, e->stream));
+    for (int a = 0; a < 4; a++) {
       if (s.np > 0) VH_CHECK(hipMemcpyAsync(dst[a], src[a], sizeof(float) * (size_t)s.np, hipMemcpyDeviceToDevice, e->stream));
     }
     VH_CHECK(hipStreamSynchronize(e->stream));
-    for (int a = 0; a < 8; a++) (void)hipFree(src[a]);
+    free_particles(s.p);
     s.p = bigger;
-    if (s.aux.dx) {
-      float *aux[8] = {s.aux.dx, s.aux.dy, s.aux.dz, reinterpret_cast<float *>(s.aux.i), s.aux.ux, s.aux.uy, s.aux.uz, s.aux.q};
-      for (float *a : aux) (void)hipFree(a);
-      s.aux = ParticlesK{};
-    }
+    if (s.aux.r) free_particles(s.aux);
     if (s.tag) {
       int64_t *t = nullptr, *t2 = nullptr;
       VH_CHECK(hipMalloc(&t, sizeof(int64_t) * max_np)); VH_CHECK(hipMalloc(&t2, sizeof(int64_t) * max_np));
@@ -690,16 +720,10 @@ void tail_copy_back_kernel(ParticlesK dst, ParticlesK src, const int64_t *tsrc, 
                            const int *__restrict__ n_live) {
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= n) return;
-  if (k >= *n_live) { dst.i[k] = -1; return; }            // the tail held dead slots: they gather at its end
-  dst.dx[k] = src.dx[k]; dst.dy[k] = src.dy[k]; dst.dz[k] = src.dz[k]; dst.i[k] = src.i[k];
+  if (k >= *n_live) { record_set_cell(dst.r, k, -1); return; }            // the tail held dead slots: they gather at its end
+  dst.r[k] = src.r[k];
   dst.ux[k] = src.ux[k]; dst.uy[k] = src.uy[k]; dst.uz[k] = src.uz[k]; dst.q[k] = src.q[k];
   if (tsrc) { tdst[k] = tsrc[k]; t2dst[k] = t2src[k]; }
-}
-
-static ParticlesK offset_particles(const ParticlesK &p, int64_t at) {
-  ParticlesK r = p;
-  r.dx += at; r.dy += at; r.dz += at; r.i += at; r.ux += at; r.uy += at; r.uz += at; r.q += at;
-  return r;
 }
 
 int k_tail_sort(Engine *e, Species &s) {
@@ -709,7 +733,7 @@ int k_tail_sort(Engine *e, Species &s) {
   const int n1 = tk.ntiles * TILE_CELLS + 1;
   const int n = (int)(s.np - s.n_sorted), nb = (n1 + 1023) / 1024;
   if (!s.ttail) VH_CHECK(hipMalloc(&s.ttail, sizeof(int) * s.tpart_count));
-  if (!s.aux.dx && alloc_particles(s.aux, s.max_np)) return 1;
+  if (!s.aux.r && alloc_particles(s.aux, s.max_np)) return 1;
   if (s.has_tags && !s.tag_aux) {
     VH_CHECK(hipMalloc(&s.tag_aux, sizeof(int64_t) * s.max_np));
     VH_CHECK(hipMalloc(&s.tag2_aux, sizeof(int64_t) * s.max_np));
@@ -718,7 +742,7 @@ int k_tail_sort(Engine *e, Species &s) {
   const int64_t *tin = s.has_tags ? s.tag + s.n_sorted : nullptr, *t2in = s.has_tags ? s.tag2 + s.n_sorted : nullptr;
   int64_t *tout = s.has_tags ? s.tag_aux + s.n_sorted : nullptr, *t2out = s.has_tags ? s.tag2_aux + s.n_sorted : nullptr;
   VH_CHECK(hipMemsetAsync(e->sort_next, 0, sizeof(int) * n1, e->stream));
-  hipLaunchKernelGGL(sort_count_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, e->stream, in.i, n, e->sort_next, tk);
+  hipLaunchKernelGGL(sort_count_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, e->stream, (const float4 *)in.r, n, e->sort_next, tk);
   hipLaunchKernelGGL(scan_local_kernel, dim3(nb), dim3(256), 0, e->stream, e->sort_next, s.ttail, e->scan_tmp, n1);
   hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(256), 0, e->stream, e->scan_tmp, nb);
   hipLaunchKernelGGL(scan_add_kernel, dim3(nb), dim3(256), 0, e->stream, s.ttail, e->sort_next, e->scan_tmp, n1);
@@ -738,17 +762,17 @@ int k_tail_sort(Engine *e, Species &s) {
 // (0 right after a sort), counted on every 8th block of 256 particles: 0.5 B per particle of traffic.
 // vpic_hip_step's adaptive sorting looks at it.
 __global__ __launch_bounds__(256)
-void disorder_kernel(const int *__restrict__ cell, int np, int *__restrict__ count) {
+void disorder_kernel(const float4 *__restrict__ rec, int np, int *__restrict__ count) {
   const long long idx = (long long)blockIdx.x * 2048 + threadIdx.x;
   bool descent = false;
-  if (idx < np && threadIdx.x > 0) descent = cell[idx] < cell[idx - 1];
+  if (idx < np && threadIdx.x > 0) descent = record_cell(rec, idx) < record_cell(rec, idx - 1);
   const int n = __popcll(__ballot(descent));
   if ((threadIdx.x & 63) == 0 && n) atomicAdd(count, n);
 }
 int k_measure_disorder(Engine *e, Species &s, int slot) {
   VH_CHECK(hipMemsetAsync(e->counters + C_DISORDER, 0, sizeof(int), e->stream));
   if (s.np > 0) {
-    hipLaunchKernelGGL(disorder_kernel, dim3((unsigned)((s.np + 2047) / 2048)), dim3(256), 0, e->stream, s.p.i, (int)s.np, e->counters + C_DISORDER);
+    hipLaunchKernelGGL(disorder_kernel, dim3((unsigned)((s.np + 2047) / 2048)), dim3(256), 0, e->stream, (const float4 *)s.p.r, (int)s.np, e->counters + C_DISORDER);
     VH_CHECK(hipGetLastError());
   }
   VH_CHECK(hipMemcpyAsync(&e->host_miss[slot], e->counters + C_DISORDER, sizeof(int), hipMemcpyDeviceToHost, e->stream));
@@ -838,9 +862,10 @@ void boundary_classify_kernel(ParticlesK p, const vpic_particle_mover_t *__restr
   const vpic_particle_mover_t m = pm[t];
   bool parked = false;
   const int idx = m.i, new_np = np - nm;
-  const float dx = p.dx[idx], dy = p.dy[idx], dz = p.dz[idx];
+  const float4 rec = p.r[idx];
+  const float dx = rec.x, dy = rec.y, dz = rec.z;
   const float ux = p.ux[idx], uy = p.uy[idx], uz = p.uz[idx], q = p.q[idx];
-  const int pi = p.i[idx];
+  const int pi = record_cell(rec);
   bool absorb = true;                          // boundary_p.c:312-316: unknown interactions absorb
   for (int face = 0; face < 6; face++) {
     const int axis = face % 3, hi = face >= 3;
@@ -930,7 +955,7 @@ void boundary_classify_kernel(ParticlesK p, const vpic_particle_mover_t *__restr
   if (nm_dev) {
     // device-resident exchange: the slot is marked dead and stays where it is (Species::n_holes, engine.h) -- nothing
     // moves under a push that is still to come, and the tile order keeps its ranges
-    if (!parked) p.i[idx] = -1;
+    if (!parked) record_set_cell(p.r, idx, -1);
     const unsigned long long gone = __ballot(!parked);          // (the lanes that got here; one atomic per wavefront)
     if (gone && (int)(threadIdx.x & 63) == __ffsll((long long)gone) - 1) atomicAdd(&counters[C_NHOLE + sp_id], __popcll(gone));
     return;
@@ -987,7 +1012,7 @@ __global__ void boundary_backfill_kernel(ParticlesK p, int64_t *tag, int64_t *ta
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= counters[C_HOLES]) return;
   const int d = holes[t], s = fills[t];
-  p.dx[d] = p.dx[s]; p.dy[d] = p.dy[s]; p.dz[d] = p.dz[s]; p.i[d] = p.i[s];
+  p.r[d] = p.r[s];
   p.ux[d] = p.ux[s]; p.uy[d] = p.uy[s]; p.uz[d] = p.uz[s]; p.q[d] = p.q[s];
   if (tag) { tag[d] = tag[s]; tag2[d] = tag2[s]; }
 }
@@ -1119,7 +1144,7 @@ void boundary_inject_kernel(const SpeciesTable *__restrict__ Tp, const vpic_part
   int pi = inj.i;
   const int stuck = move_p_lane<false>(dx, dy, dz, pi, ux, uy, uz, inj.q, mx, my, mz, nullptr, g_acc, NO_WINDOW, g, false, det_scale);   // (det_scale != 0: g_acc is the fixed-point accumulator)
   const ParticlesK p = Tp->p[s];
-  p.dx[idx] = dx; p.dy[idx] = dy; p.dz[idx] = dz; p.i[idx] = pi;
+  p.r[idx] = make_record(dx, dy, dz, pi);
   p.ux[idx] = ux; p.uy[idx] = uy; p.uz[idx] = uz; p.q[idx] = inj.q;
   // an injector record has no tag fields (species_advance.h:48-55): a migrating particle arrives untagged; a
   // particle the host injects with an age brings its tags along

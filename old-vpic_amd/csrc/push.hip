@@ -32,13 +32,14 @@
 //   * cell-crossers are queued per wavefront in LDS (36 bytes each) and finished 64 at a time in a wave-synchronous,
 //     branch-free restatement of the move_p loop whose per-segment deposits go through the same scan;
 //   * the accumulator array is a single copy: there is no per-pipeline replica to reduce.
-// No MFMA: there is no dense contraction on this path.  HBM traffic by design: 32 B read + 24 B written per particle
-// (i and q are not rewritten for in-cell particles).
+// No MFMA: there is no dense contraction on this path.  HBM traffic by design: 32 B read + 28 B written per particle
+// (q is not rewritten; the cell is, with the position, as one 16-byte record: engine.h, ParticlesK).
 //
 // Build note: -fno-slp-vectorize is required.  With the SLP vectorizer on, hipcc (ROCm 7.2) packs
 // pairs of these fp32 operations into v_pk_mul_f32/v_pk_add_f32 and the kernel returns wrong
 // momenta/positions on gfx950 (caught by the golden-vector tests).
 #include "push_device.h"
+#include "record_offsets.h"
 #include <cstdlib>
 #include <cstring>
 #include <cstddef>
@@ -76,7 +77,7 @@ struct PushParams {
   ParticlesK out; int *next;
   int stage;           // STAGE instances: 1 = the positions of a pass wait in registers for its cell-crossers (see Staged below); 0 = stored at once
 #ifdef VPIC_HIP_ABLATION
-  int ablate;   // timing experiments only (builds with -DVPIC_HIP_ABLATION: VPIC_HIP_ABLATE; tools/ablate.sh): 1 no in-cell deposit, 2 no mover path, 4 no interpolator gather, 8 no flush, 16 no lane regrouping, 32 no mover deposit, 64 no drain, 128 no in-cell stores
+  int ablate;   // timing experiments only (builds with -DVPIC_HIP_ABLATION: VPIC_HIP_ABLATE; tools/ablate.sh): 1 no in-cell deposit, 2 no mover path, 4 no interpolator gather, 8 no flush, 16 no lane regrouping, 32 no mover deposit, 64 no drain, 128 no in-cell stores, 256 no late stores of the crossers' records
 #endif
 };
 
@@ -98,13 +99,30 @@ struct PushParams {
     SEG_STEP(a[9], flag, CTRL); SEG_STEP(a[10], flag, CTRL); SEG_STEP(a[11], flag, CTRL);         \
   } while (0)
 
-// Particle arrays are addressed as (uniform base pointer in SGPRs) + (32-bit byte offset in one
-// VGPR): every access then uses the scalar-base form of global_load/global_store and the eight
-// arrays share one offset register instead of eight 64-bit address computations.
+// Particle arrays are addressed as (uniform base pointer in SGPRs) + (32-bit byte offset in a
+// VGPR): every access then uses the scalar-base form of global_load/global_store, the four 4-byte
+// arrays share one offset register and the position records take that offset times four.  The bases
+// are those of the WORKGROUP's first particle (record_offsets.h: a record offset from the array's
+// start would wrap from 2^28 particles on).
+typedef float rec4 __attribute__((ext_vector_type(4)));           // a position record {dx, dy, dz, i} as one 16-byte access
+__device__ __forceinline__ rec4 ldr(const float4 *base, unsigned off) { return *reinterpret_cast<const rec4 *>(reinterpret_cast<const char *>(base) + off); }
+__device__ __forceinline__ void str(float4 *base, unsigned off, float x, float y, float z, int i) {
+  rec4 v; v.x = x; v.y = y; v.z = z; v.w = __int_as_float(i);
+  *reinterpret_cast<rec4 *>(reinterpret_cast<char *>(base) + off) = v;
+}
+__device__ __forceinline__ void str_nt(float4 *base, unsigned off, float x, float y, float z, int i) {
+  rec4 v; v.x = x; v.y = y; v.z = z; v.w = __int_as_float(i);
+  __builtin_nontemporal_store(v, reinterpret_cast<rec4 *>(reinterpret_cast<char *>(base) + off));
+}
+// ... anywhere in the array (SORT: a particle's place in the new order): a 64-bit address, record_address() of
+// record_offsets.h as pointer arithmetic (through an integer the pointer would lose its address space and the store turn FLAT)
+__device__ __forceinline__ rec4 *rec_at(float4 *base, unsigned dst) {
+  return reinterpret_cast<rec4 *>(reinterpret_cast<char *>(base) + ((uint64_t)dst << RECORD_SHIFT));
+}
+// the cell word of a record alone (the window's sample, the SORT instance's pre-count)
+__device__ __forceinline__ int ldcell(const float4 *base, unsigned off) { return __float_as_int(*reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + off + 12u)); }
 __device__ __forceinline__ float ldf(const float *base, unsigned off) { return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + off); }
-__device__ __forceinline__ int ldi(const int *base, unsigned off) { return *reinterpret_cast<const int *>(reinterpret_cast<const char *>(base) + off); }
 __device__ __forceinline__ void stf(float *base, unsigned off, float v) { *reinterpret_cast<float *>(reinterpret_cast<char *>(base) + off) = v; }
-__device__ __forceinline__ void sti(int *base, unsigned off, int v) { *reinterpret_cast<int *>(reinterpret_cast<char *>(base) + off) = v; }
 // NON-TEMPORAL stores (round 4) for what the launch writes once and never touches again: the momenta of the main pass and the
 // crossers' late stores (after them the line is complete).  Their lines then leave L2 first, and the position lines that the late
 // stores will hit stay longer.  Same-box A/B at 256^3 x 64 ppc, three script runs: momenta +0.3-0.7 %, with the late stores
@@ -113,7 +131,6 @@ __device__ __forceinline__ void sti(int *base, unsigned off, int v) { *reinterpr
 // that sorts as it pushes (45 ms against 26: its runs end inside sectors, and the pieces no longer meet in L2), the momenta of
 // the hot instances whose positions wait in registers (level: 1.41-1.43 ms either way on the configs[3] slab).
 __device__ __forceinline__ void stf_nt(float *base, unsigned off, float v) { __builtin_nontemporal_store(v, reinterpret_cast<float *>(reinterpret_cast<char *>(base) + off)); }
-__device__ __forceinline__ void sti_nt(int *base, unsigned off, int v) { __builtin_nontemporal_store(v, reinterpret_cast<int *>(reinterpret_cast<char *>(base) + off)); }
 
 
 // A wave-uniform value parked in a VECTOR register.  The pass loop needs more scalars than the 102 SGPRs hold; what the
@@ -377,8 +394,9 @@ __device__ __forceinline__ void mover_streak12(float *a, float q, float mx, floa
 
 // ---- positions that wait for their cell-crossers (round 4) ------------------------------------------------------------
 // A cell-crosser's final position and cell are known only when its move is done, passes after the one that pushed it; stored
-// then, they are four scattered 4-byte stores into lines the pass wrote long before -- a 64-byte write request each for
-// 4 bytes.  Measured on one launch (tools/ablate_once.py): 20 % of a hot charged species' launch, 28 % of a charge-0 copy's,
+// then, they were four scattered 4-byte stores into lines the pass wrote long before -- a 64-byte write request each for
+// 4 bytes (one 16-byte store of the position record since: engine.h, ParticlesK).  Measured on one launch, with the four
+// stores (tools/ablate_once.py): 20 % of a hot charged species' launch, 28 % of a charge-0 copy's,
 // 8 % of a cold beam's.  Where half the particles cross (the hot species: sorted by tile only, pushed without regrouping, so
 // lane l of a pass holds particle base + l) the queue fills every other pass anyway: the positions of up to STAGE_CAP passes
 // stay in registers, the batch is finished, and the passes' positions are stored ONCE, whole spans, the crossers' final values
@@ -394,8 +412,11 @@ struct StagePark { int base[STAGE_CAP], qb[STAGE_CAP]; unsigned cm_lo[STAGE_CAP]
 constexpr int STAGED_BIT = 31;                                   // of the queue entry's voxel word: the crosser's pass is waiting for it
 struct Straggler { float4 pos_i, disp_idx; float q; bool live; unsigned long long again; };   // a crosser still on its way after a batch's rounds
 
-template <bool FAST, class W, bool HIST = false, bool STAGE = false>
-__device__ __forceinline__ int drain_wave(const ParticlesK &p, WaveQueue *mq, const int n_mq,
+// p: the arrays rebased to particle `rel` (the workgroup's first: the queued idx are the launch's, idx - rel is the slot);
+// WIDE (the SORT instance): the arrays of the second buffer from their start, rel = 0, idx a place anywhere in the new order
+// (below 2^30: the 4-byte arrays take it as a 32-bit offset, the record gets a 64-bit address).
+template <bool FAST, class W, bool HIST = false, bool STAGE = false, bool WIDE = false>
+__device__ __forceinline__ int drain_wave(const ParticlesK &p, const int rel, WaveQueue *mq, const int n_mq,
                                           const int lane, typename W::acc_t *s_acc, float *g_acc, const int wbase,
                                           const DrainParams *dp, const int ablate, const int max_round, const int idx_base,
                                           MissList *ml, int &n_miss, const double det_scale = 0, const HistK *hk = nullptr, Straggler *sg = nullptr) {
@@ -428,7 +449,7 @@ __device__ __forceinline__ int drain_wave(const ParticlesK &p, WaveQueue *mq, co
     const float q = mq->q[kq];
     vpic_particle_mover_t m; m.dispx = c2.x; m.dispy = c2.y; m.dispz = c2.z; m.i = __float_as_int(c2.w);
     const int idx = m.i;
-    const unsigned o4 = (unsigned)idx << 2;
+    const unsigned o4 = word_offset(idx, rel);
     float dx = c0.x, dy = c0.y, dz = c0.z;
     int flips = (__float_as_int(c0.w) >> FLIP_SHIFT) & 7;          // momentum components negated by reflections so far (x 1, y 2, z 4)
     const bool staged = STAGE && live && (__float_as_int(c0.w) >> STAGED_BIT) & 1;   // its pass has not stored its positions yet: the result goes to the queue slot
@@ -558,10 +579,14 @@ __device__ __forceinline__ int drain_wave(const ParticlesK &p, WaveQueue *mq, co
     }
     n_again = __popcll(again);
     if (mine && !live) {
-#ifdef VPIC_HIP_ABLATION   // 256: no stores of the crossers' final positions; 512: one of the four only (what a float4 position record would issue)
-      if (ablate & 256) {} else if (ablate & 512) { stf(p.dx, o4, dx + dy + dz + __int_as_float(pi)); } else
+#ifdef VPIC_HIP_ABLATION   // 256: no store of the crossers' final records
+      if (ablate & 256) {} else
 #endif
-      if (!staged) { stf_nt(p.dx, o4, dx); stf_nt(p.dy, o4, dy); stf_nt(p.dz, o4, dz); sti_nt(p.i, o4, pi); }
+      // THE LATE STORE: position and cell in one 16-byte record, half a sector of a line the main pass wrote whole
+      if (!staged) {
+        if (WIDE) { rec4 v; v.x = dx; v.y = dy; v.z = dz; v.w = __int_as_float(pi); __builtin_nontemporal_store(v, rec_at(p.r, (unsigned)idx)); }
+        else str_nt(p.r, o4 << 2, dx, dy, dz, pi);
+      }
       if (HIST) hist_count<W>(*hk, pi, wbase, gsy, gsz, td);       // (a particle stopped on a face still sits in the array, in cell pi)
       if (flips) {   // the momenta are where the pass that queued the particle stored them (this wavefront, earlier): wait, then negate in place
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -684,7 +709,7 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
     follow = P.follow > 0 || flag == 1u;
   }
   if (follow && wave == 0 && last > first)
-    sample = p.i[first + (int)(((long long)lane * (last - first)) >> 6)];            // (in flight while the window is cleared)
+    sample = record_cell(p.r, (long long)first + (int)(((long long)lane * (last - first)) >> 6));            // (in flight while the window is cleared)
   if (!CHARGELESS)
     for (int k = tid; k < 12 * NSLOT_PAD; k += PUSH_THREADS) s_acc[k] = 0;
   if (HIST)
@@ -725,7 +750,7 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
     // window with them; the median ignores them.)
     const int chunk_n = min(WAVES * wave_span, P.np - first);
     const int sidx = first + (int)(((long long)lane * chunk_n) >> 6);
-    const int k0 = p.i[sidx];
+    const int k0 = record_cell(p.r, sidx);
     int rank = 0;                                      // sample keys below mine (ties by lane)
     for (int l = 0; l < 64; l++) {
       const int kl = __builtin_amdgcn_readlane(k0, l);
@@ -755,7 +780,6 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
     vtd.mul_sz = (unsigned)in_vgpr((int)P.mul_sz); vtd.sh_sz = (unsigned)in_vgpr((int)P.sh_sz);
     vsy = in_vgpr(gsy); vsz = in_vgpr(gsz);
   }
-  const int vnp1 = TILE ? in_vgpr(P.np - 1) : P.np - 1;
   HistK hk;
   if (HIST || SORT) {
     hk.hist = P.hist; hk.s_cnt = s_cnt;
@@ -770,6 +794,10 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
   int n_pend = 0;                                      // wave-uniform
   const bool stage = STAGE && P.stage != 0;            // wave-uniform (the host switches it on for species whose queue fills every other pass)
   StagePark *park = &s_park[STAGE ? wave : 0];
+  // the arrays rebased to the first particle of the segment under way (record_offsets.h); whatever is queued is finished
+  // before the base moves on
+  ParticlesK pw = p;
+  int rel = 0;
   // Finish what is queued and store the positions of the passes that wait: ONE round normally (see drain_wave), every round it
   // takes when `all`.  Returns the queue's new length (the stragglers).
   auto drain_release = [&](const bool all) -> int {
@@ -777,7 +805,7 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
     int n_back = 0;
     if (n_mq > 0) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      n_back = drain_wave<FAST, W, HIST, STAGE>(p, mq, n_mq, lane, s_acc, g_acc, wbase, dp, ablate, all ? (1 << 30) : StageRounds<CHARGELESS>::value, P.idx_base, ml, n_miss, td.scale, &hk, &sg);
+      n_back = drain_wave<FAST, W, HIST, STAGE>(pw, rel, mq, n_mq, lane, s_acc, g_acc, wbase, dp, ablate, all ? (1 << 30) : StageRounds<CHARGELESS>::value, P.idx_base, ml, n_miss, td.scale, &hk, &sg);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     }
 #pragma unroll
@@ -794,10 +822,8 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
         const int newi = __float_as_int(r.w);
         if (newi >= 0) { fx = r.x; fy = r.y; fz = r.z; fi_ = newi; }
       }
-      const unsigned o4 = (unsigned)(pb + lane) << 2;
-      // the cells as a whole span as well: where half the particles change cell every sector of the span holds a new value, and a
-      // whole sector is one write where 4 bytes of it are a read-modify-write of the memory's own
-      if ((actj >> lane) & 1ull) { stf(p.dx, o4, fx); stf(p.dy, o4, fy); stf(p.dz, o4, fz); sti(p.i, o4, fi_); }
+      // positions and cells as whole spans of records: where half the particles change cell every sector of the span holds a new value
+      if ((actj >> lane) & 1ull) str(pw.r, record_offset(pb + lane, rel), fx, fy, fz, fi_);
     }
     n_pend = 0;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // (the results were read: the slots may be written again)
@@ -824,9 +850,9 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
 #pragma unroll 1
       for (int base = sfirst + wave * 64; base < slast; base += AHEAD * PUSH_THREADS) {     // (wave-uniform bounds)
         int keys[AHEAD];
-        const int *const cell = p.i;
+        const float4 *const recs = p.r + sfirst;               // (the keys at a 16-byte stride, from the segment's base)
 #pragma unroll
-        for (int j = 0; j < AHEAD; j++) { const int at = base + j * PUSH_THREADS + lane; keys[j] = at < slast ? ldi(cell, (unsigned)at << 2) : -1; }
+        for (int j = 0; j < AHEAD; j++) { const int at = base + j * PUSH_THREADS + lane; keys[j] = at < slast ? ldcell(recs, record_offset(at, sfirst)) : -1; }
 #pragma unroll
         for (int j = 0; j < AHEAD; j++) {
           const int key = keys[j];
@@ -866,20 +892,31 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
   constexpr int PASS_STRIDE = 64;
   const int wave_first = sfirst + wave * sspan;
   const int wave_last = TILE ? min(slast, wave_first + sspan) : slast;     // TILE: the next wavefront's (or tile's) particles begin here
-  float r_dx, r_dy, r_dz, r_ux, r_uy, r_uz, r_q;
-  int r_key;
+  // the segment's base (wave-uniform, 64-bit): every offset below is relative to particle sfirst.  Crossers queued under
+  // the base of the segment before are finished first (TILE: the appended share of a tile, rare)
+  if (TILE && !SORT && seg && (n_mq > 0 || (STAGE && n_pend > 0))) {     // (STAGE: a pass may wait with no crosser queued: its base is the old one too)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if constexpr (STAGE) n_mq = drain_release(true);
+    else n_mq = drain_wave<FAST, W, HIST>(pw, rel, mq, n_mq, lane, s_acc, g_acc, wbase, dp, ablate, 1 << 30, P.idx_base, ml, n_miss, td.scale, &hk);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  }
+  pw = offset_particles(p, sfirst);
+  rel = SORT ? 0 : sfirst;                               // (SORT: the queue holds places in the second buffer, addressed from its start)
+  const int vrel_max = TILE ? in_vgpr(P.np - 1 - sfirst) : P.np - 1 - sfirst;   // the slot of the array's last particle: lanes behind it read that one
+  rec4 r_rec;
+  float r_ux, r_uy, r_uz, r_q;
   {
-    const unsigned k4 = (unsigned)min(wave_first + lane, P.np - 1) << 2;
-    r_key = ldi(p.i, k4); r_dx = ldf(p.dx, k4); r_dy = ldf(p.dy, k4); r_dz = ldf(p.dz, k4);
-    r_ux = ldf(p.ux, k4); r_uy = ldf(p.uy, k4); r_uz = ldf(p.uz, k4); r_q = ldf(p.q, k4);
+    const unsigned k4 = (unsigned)min(wave_first - sfirst + lane, P.np - 1 - sfirst) << 2;
+    r_rec = ldr(pw.r, k4 << 2);
+    r_ux = ldf(pw.ux, k4); r_uy = ldf(pw.uy, k4); r_uz = ldf(pw.uz, k4); r_q = ldf(pw.q, k4);
   }
 
 #pragma unroll 1
   for (int it = 0; it < wave_passes; it++) {
     const int base = wave_first + it * PASS_STRIDE;
     if (base >= wave_last) break;                      // wave-uniform
-    int idx = base + lane, key = (base + lane < wave_last) ? r_key : -1;      // lanes beyond the end hold a particle that is not theirs (np-1 at the end of the array)
-    float dx = r_dx, dy = r_dy, dz = r_dz, ux = r_ux, uy = r_uy, uz = r_uz, q = r_q;
+    int idx = base + lane, key = (base + lane < wave_last) ? __float_as_int(r_rec.w) : -1;      // lanes beyond the end hold a particle that is not theirs (np-1 at the end of the array)
+    float dx = r_rec.x, dy = r_rec.y, dz = r_rec.z, ux = r_ux, uy = r_uy, uz = r_uz, q = r_q;
     // regroup the 64 particles by cell: lane `dest` takes over the particle this lane loaded
     // (skipped when the cells already ascend along the lanes, the usual case right after a sort)
     const int kk = key < 0 ? 0x7fffffff : key;
@@ -930,10 +967,11 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
     const float2 fb1 = *reinterpret_cast<const float2 *>(f + 4);
     __builtin_amdgcn_sched_barrier(0);
     {
-      const int k = base + ((it + 1 < wave_passes) ? PASS_STRIDE : 0) + lane;
-      const unsigned k4 = (unsigned)min(k, vnp1) << 2;
-      r_key = ldi(p.i, k4); r_dx = ldf(p.dx, k4); r_dy = ldf(p.dy, k4); r_dz = ldf(p.dz, k4);
-      r_ux = ldf(p.ux, k4); r_uy = ldf(p.uy, k4); r_uz = ldf(p.uz, k4); r_q = ldf(p.q, k4);
+      // one record and four words: the pass waits on five operations behind its gather
+      const int k = base - sfirst + ((it + 1 < wave_passes) ? PASS_STRIDE : 0) + lane;
+      const unsigned k4 = (unsigned)min(k, vrel_max) << 2;
+      r_rec = ldr(pw.r, k4 << 2);
+      r_ux = ldf(pw.ux, k4); r_uy = ldf(pw.uy, k4); r_uz = ldf(pw.uz, k4); r_q = ldf(pw.q, k4);
     }
     __builtin_amdgcn_sched_barrier(0);
     // Branch-free pass body: every lane computes (a lane past the end of the array holds the data of particle
@@ -945,7 +983,7 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
     float sux, suy, suz;                          // the momenta as stored (advance_p.cxx:106-108)
     float spx = 0.f, spy = 0.f, spz = 0.f;        // STAGE: the positions as they would be stored now
     {
-      const unsigned o4 = (unsigned)idx << 2;
+      const unsigned o4 = word_offset(idx, sfirst);
       float v0, v1, v2, v3, v4, v5;
       if (FAST) {
         const float hax = qdt_2mc * __builtin_fmaf(dz, __builtin_fmaf(dy, fe_x.w, fe_x.z), __builtin_fmaf(dy, fe_x.y, fe_x.x));
@@ -1008,19 +1046,22 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
         if (active) {
           const unsigned d4 = (unsigned)dst << 2;
           stf(P.out.ux, d4, sux); stf(P.out.uy, d4, suy); stf(P.out.uz, d4, suz);
-          stf(P.out.dx, d4, incell ? v3 : dx); stf(P.out.dy, d4, incell ? v4 : dy); stf(P.out.dz, d4, incell ? v5 : dz);
-          sti(P.out.i, d4, key); stf(P.out.q, d4, q);
+          rec4 v; v.x = incell ? v3 : dx; v.y = incell ? v4 : dy; v.z = incell ? v5 : dz; v.w = __int_as_float(key);
+          *rec_at(P.out.r, (unsigned)dst) = v;
+          stf(P.out.q, d4, q);
         }
       } else
       if (STAGE && stage) {
         // the momenta are final; the positions wait for the pass's crossers (drain_release stores them)
-        if (!TILE || active) { stf(p.ux, o4, sux); stf(p.uy, o4, suy); stf(p.uz, o4, suz); }
+        if (!TILE || active) { stf(pw.ux, o4, sux); stf(pw.uy, o4, suy); stf(pw.uz, o4, suz); }
         // (which slot the pass waits in is decided when it is parked: a pass that would overflow the queue releases the waiting ones first)
         spx = incell ? v3 : dx; spy = incell ? v4 : dy; spz = incell ? v5 : dz;
       } else
       if ((!TILE || active) && !(ablate & 128)) {
-        stf_nt(p.ux, o4, sux); stf_nt(p.uy, o4, suy); stf_nt(p.uz, o4, suz);
-        stf(p.dx, o4, incell ? v3 : dx); stf(p.dy, o4, incell ? v4 : dy); stf(p.dz, o4, incell ? v5 : dz);
+        stf_nt(pw.ux, o4, sux); stf_nt(pw.uy, o4, suy); stf_nt(pw.uz, o4, suz);
+        // the record whole: the new position of a lane that stays, the old position and the old cell of a crosser (its late store
+        // brings the final ones); a dead slot or a lane behind the array's end writes back what it read
+        str(pw.r, o4 << 2, incell ? v3 : dx, incell ? v4 : dy, incell ? v5 : dz, key);
       }
       if (!CHARGELESS && !(ablate & 1)) {
         const float qd = (incell && active) ? q : 0.f;
@@ -1102,7 +1143,7 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
         // next batch.  Only when that does not make room for this pass's crossers (phase 0, second attempt) is the batch
         // finished whatever it takes.
         const int cap = (phase == 0 && attempt > 0) ? (1 << 30) : 1;
-        const int n_back = drain_wave<FAST, W, HIST>(SORT ? P.out : p, mq, n_now, lane, s_acc, g_acc, wbase, dp, ablate, cap, P.idx_base, ml, n_miss, td.scale, &hk);
+        const int n_back = drain_wave<FAST, W, HIST, false, SORT>(SORT ? P.out : pw, rel, mq, n_now, lane, s_acc, g_acc, wbase, dp, ablate, cap, P.idx_base, ml, n_miss, td.scale, &hk);
             const int n_left = n_mq - n_now;               // move what stayed behind to the front, after the stragglers
         const int src = lane < n_left ? 64 + lane : 0;
         const float4 t0 = mq->pos_i[src], t2 = mq->disp_idx[src];
@@ -1120,7 +1161,7 @@ void advance_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float *__rest
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // queue writes before the reads below
   if constexpr (STAGE) n_mq = drain_release(true);         // (every crosser finishes: nothing is left in the queue)
   else
-  drain_wave<FAST, W, HIST>(SORT ? P.out : p, mq, n_mq, lane, s_acc, g_acc, wbase, dp, ablate, 1 << 30, P.idx_base, ml, n_miss, td.scale, &hk);
+  drain_wave<FAST, W, HIST, false, SORT>(SORT ? P.out : pw, rel, mq, n_mq, lane, s_acc, g_acc, wbase, dp, ablate, 1 << 30, P.idx_base, ml, n_miss, td.scale, &hk);
   if (!CHARGELESS && !DET) flush_misses(ml, n_miss, g_acc, lane);
 
   // how many particles left their cell (the host picks the window instance and the sort policy from it)
@@ -1254,7 +1295,7 @@ extern "C" int vpic_hip_push_plan(int64_t np, int iters, int64_t *start, int32_t
   if (np < 0 || iters < 1 || iters > PUSH_ITERS || max_segments < 1) return -1;
   const int64_t per_chunk = (int64_t)PUSH_THREADS * iters;
   // a launch of c particles addresses up to particle c + 62 (the lanes of a last, partly filled pass): (c + 63) * 4 < 2^32
-  int64_t seg = (((int64_t)1 << 30) - 64) / per_chunk * per_chunk;
+  int64_t seg = push_segment_particles(per_chunk);
   if (np <= ((int64_t)1 << 30) && (np % 64 == 0 || np <= ((int64_t)1 << 30) - 64)) seg = (np + per_chunk - 1) / per_chunk * per_chunk;   // fits one launch
   int n = 0;
   for (int64_t at = 0; at < np; at += seg, n++) {
@@ -1331,7 +1372,7 @@ int k_advance_p(Engine *e, Species &s, bool async, int phase) {
     in.tail_sort_min = e->knobs.tail_sort_min; in.no_tail_sort = e->knobs.no_tail_sort;
     in.wx[0] = Window<false>::WX; in.wx[1] = Window<true>::WX; in.wmargin = WMARGIN; in.threads = PUSH_THREADS; in.max_iters = PUSH_ITERS;
     in.tile_valid = s.tile_valid; in.chargeless = s.chargeless; in.coarse_sorted = s.coarse_sorted; in.det_acc = e->det_acc; in.time_kernels = e->time_kernels;
-    in.fuse_pending = s.fuse_pending; in.hist_request = s.hist_request; in.hist_valid = s.hist_valid; in.fuse_buffers = s.aux.dx && s.tpart2;
+    in.fuse_pending = s.fuse_pending; in.hist_request = s.hist_request; in.hist_valid = s.hist_valid; in.fuse_buffers = s.aux.r && s.tpart2;
     P.iters = push_passes(s.pol, in);
     int64_t seg_start[4]; int32_t seg_count[4]; uint32_t seg_grid[4];
     const int n_seg = vpic_hip_push_plan(s.np, P.iters, seg_start, seg_count, seg_grid, 4);
@@ -1362,6 +1403,10 @@ int k_advance_p(Engine *e, Species &s, bool async, int phase) {
       P.ntx = tk.ntx; P.nty = tk.nty; P.ntiles = tk.ntiles;
       P.mul_sy = tk.mul_sy; P.sh_sy = tk.sh_sy; P.mul_sz = tk.mul_sz; P.sh_sz = tk.sh_sz;
       const int64_t behind = s.np > s.n_sorted ? s.np - s.n_sorted : 0;
+      // What a workgroup reaches from its base (record_offsets.h): a tile's range stays far below 2^28 particles -- plan_push
+      // leaves the tile order long before (a tile of more than np / 320 particles counts as clumped) -- and a tile's share of
+      // the appended particles is at most all of them
+      if (!span_in_reach(0, behind)) VH_FAIL("advance_p: %lld particles appended since the last sort; sort the species first", (long long)behind);
       if (phase != 2 && pl.regroup_tail && k_tail_sort(e, s)) return 1;
       if (phase != 2) s.tail_regrouped = pl.regroup_tail && s.tail_sorted;
       P.ttail = s.tail_regrouped ? s.ttail : nullptr;
@@ -1391,8 +1436,7 @@ int k_advance_p(Engine *e, Species &s, bool async, int phase) {
 #define PUSH_LAUNCH(...) launch_push<__VA_ARGS__>(e->push_fast, seg_grid[g], e->stream, ps, reinterpret_cast<const float4 *>(e->fi), g_acc, s.drain_k, P); break
     for (int g = 0; g < n_seg; g++) {
       const int64_t at = seg_start[g];
-      ParticlesK ps = s.p;
-      ps.dx += at; ps.dy += at; ps.dz += at; ps.i += at; ps.ux += at; ps.uy += at; ps.uz += at; ps.q += at;
+      const ParticlesK ps = offset_particles(s.p, at);
       P.np = seg_count[g]; P.idx_base = (int)at;
       switch (pl.instance) {
         case PushInstance::chargeless: PUSH_LAUNCH(true);
@@ -1453,9 +1497,10 @@ void energy_p_kernel(ParticlesK p, const float4 *__restrict__ fi, double *__rest
   double en = 0;
   const float one = 1.f;
   for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < np; idx += (long long)gridDim.x * 256) {   // (a species may hold close to 2^31 particles)
-    if (p.i[idx] < 0) continue;                          // a dead slot (engine.h, Species::n_holes)
-    const float dx = p.dx[idx], dy = p.dy[idx], dz = p.dz[idx];
-    const float4 *f = fi + (size_t)p.i[idx] * 5;
+    const float4 rec = p.r[idx];
+    if (record_cell(rec) < 0) continue;                  // a dead slot (engine.h, Species::n_holes)
+    const float dx = rec.x, dy = rec.y, dz = rec.z;
+    const float4 *f = fi + (size_t)record_cell(rec) * 5;
     const float4 fe_x = f[0], fe_y = f[1], fe_z = f[2];
     float v0 = p.ux[idx] + qdt_2mc * ((fe_x.x + dy * fe_x.y) + dz * (fe_x.z + dy * fe_x.w));
     float v1 = p.uy[idx] + qdt_2mc * ((fe_y.x + dz * fe_y.y) + dx * (fe_y.z + dz * fe_y.w));
@@ -1494,12 +1539,14 @@ template <bool UNCENTER>
 __global__ __launch_bounds__(256)
 void center_p_kernel(ParticlesK p, const float4 *__restrict__ fi, float args_qdt_2mc, int np) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= np || p.i[idx] < 0) return;
+  if (idx >= np) return;
+  const float4 rec = p.r[idx];
+  if (record_cell(rec) < 0) return;
   const float qdt_2mc = UNCENTER ? -args_qdt_2mc : args_qdt_2mc;
   const float qdt_4mc = UNCENTER ? (float)(-0.5 * args_qdt_2mc) : (float)(0.5 * args_qdt_2mc);
   const float one = 1.f, one_third = 1. / 3., two_fifteenths = 2. / 15.;
-  const float dx = p.dx[idx], dy = p.dy[idx], dz = p.dz[idx];
-  const float4 *f = fi + (size_t)p.i[idx] * 5;
+  const float dx = rec.x, dy = rec.y, dz = rec.z;
+  const float4 *f = fi + (size_t)record_cell(rec) * 5;
   const float4 fe_x = f[0], fe_y = f[1], fe_z = f[2], fb0 = f[3];
   const float2 fb1 = *reinterpret_cast<const float2 *>(f + 4);
   const float hax = qdt_2mc * ((fe_x.x + dy * fe_x.y) + dz * (fe_x.z + dy * fe_x.w));
@@ -1545,10 +1592,12 @@ namespace vpichip {
 __global__ __launch_bounds__(256)
 void accumulate_hydro_p_kernel(float *__restrict__ h0, ParticlesK p, const float4 *__restrict__ fi, int np, HydroConsts hc, int sy, int sz) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= np || p.i[idx] < 0) return;
-  const int ii = p.i[idx];
+  if (idx >= np) return;
+  const float4 rec = p.r[idx];
+  const int ii = record_cell(rec);
+  if (ii < 0) return;
   HydroP P;
-  hydro_particle(p.dx[idx], p.dy[idx], p.dz[idx], p.ux[idx], p.uy[idx], p.uz[idx], p.q[idx], load_interp(fi, ii), hc, P);
+  hydro_particle(rec.x, rec.y, rec.z, p.ux[idx], p.uy[idx], p.uz[idx], p.q[idx], load_interp(fi, ii), hc, P);
   float *h = h0 + (size_t)ii * HYDRO_STRIDE;
 #pragma unroll
   for (int n = 0; n < 8; n++) {
@@ -1579,7 +1628,8 @@ void accumulate_hydro_cells_kernel(float *__restrict__ h0, ParticlesK p, const f
 #pragma unroll 1
   for (int idx = first; idx < last; idx++) {
     HydroP P;
-    hydro_particle(p.dx[idx], p.dy[idx], p.dz[idx], p.ux[idx], p.uy[idx], p.uz[idx], p.q[idx], f, hc, P);
+    const float4 rec = p.r[idx];
+    hydro_particle(rec.x, rec.y, rec.z, p.ux[idx], p.uy[idx], p.uz[idx], p.q[idx], f, hc, P);
 #pragma unroll
     for (int n = 0; n < 8; n++) {
       float c[HYDRO_MOMENTS];

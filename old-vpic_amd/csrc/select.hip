@@ -141,8 +141,9 @@ void select_write_kernel(ParticlesK p, const int64_t *__restrict__ tag, const in
       const long long dest = offset + s_before[group] + __popcll(m & ((1ull << lane) - 1ull));
       if (dest >= cap) continue;
       const long long idx = c * SEL_CHUNK + (long long)group * 64 + lane;    // (below np: the bit is set for live particles only)
-      const int voxel = p.i[idx];
-      const float dx = p.dx[idx], dy = p.dy[idx], dz = p.dz[idx];
+      const float4 pos = p.r[idx];
+      const int voxel = record_cell(pos);
+      const float dx = pos.x, dy = pos.y, dz = pos.z;
       if (out_p) {
         float4 *rec = reinterpret_cast<float4 *>(out_p + dest);              // 48 bytes: three 16-byte stores
         rec[0] = make_float4(dx, dy, dz, __int_as_float(voxel));

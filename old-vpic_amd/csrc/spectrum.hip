@@ -59,7 +59,7 @@ __device__ __forceinline__ void flush_window(unsigned *win, int base, const Spec
 // stats[0]: live particles seen, stats[1]: misses.
 template <bool TILE>
 __global__ __launch_bounds__(64 * SPEC_WAVES)
-void energy_spectrum_kernel(const int *__restrict__ pi, const float *__restrict__ pux, const float *__restrict__ puy,
+void energy_spectrum_kernel(const float4 *__restrict__ prec, const float *__restrict__ pux, const float *__restrict__ puy,
                             const float *__restrict__ puz, long long np, long long chunk, SpectrumK k, GridK g, TileK t,
                             unsigned *__restrict__ lin, unsigned long long *__restrict__ logc,
                             unsigned long long *__restrict__ stats) {
@@ -76,7 +76,7 @@ void energy_spectrum_kernel(const int *__restrict__ pi, const float *__restrict_
   unsigned long long n_seen = 0, n_miss = 0;
   for (long long at = begin; at < end; at += 64) {
     const long long idx = at + lane;
-    const int voxel = idx < end ? pi[idx] : -1;
+    const int voxel = idx < end ? record_cell(prec, idx) : -1;   // (the cell word of the position record: a 16-byte stride)
     const bool live = voxel >= 0 && voxel < g.nv;                            // i < 0: a dead slot (engine.h, Species::n_holes)
     n_seen += __popcll(__ballot(live));
     if (!__any(live)) continue;
@@ -162,7 +162,7 @@ int k_energy_spectrum(Engine *e, Species &s, const vpic_hip_spectrum_t &sp) {
     const size_t lds = sizeof(unsigned) * ((size_t)sp.n_log + (size_t)SPEC_WAVES * k.win * sp.n_lin);
     const TileK tk = make_tile_k(e->gk);
     auto kernel = s.tile_valid ? energy_spectrum_kernel<true> : energy_spectrum_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)ch.groups), dim3(64 * SPEC_WAVES), lds, e->stream, s.p.i, s.p.ux, s.p.uy, s.p.uz,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)ch.groups), dim3(64 * SPEC_WAVES), lds, e->stream, (const float4 *)s.p.r, s.p.ux, s.p.uy, s.p.uz,
                        (long long)s.np, ch.chunk, k, e->gk, tk, e->spec_lin, e->spec_log, e->spec_stats.dev);
     VH_CHECK(hipGetLastError());
   }

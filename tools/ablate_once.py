@@ -5,7 +5,7 @@ launch starts from is the real one, which a whole run with parts off cannot offe
 re-crosses the same particles every step).  Needs a -DVPIC_HIP_ABLATION build: VPIC_HIP_LIB=tools/ab/libablation.so.
     python tools/ablate_once.py [--deck two-stream|trecon] [--grid nx ny nz] [--ppc n] [--steps-before n] bits [bits ...]
 bits (push.hip): 1 no in-cell deposit, 2 no crossing path, 4 no interpolator gather, 8 no flush, 16 no regrouping,
-32 no mover deposit, 64 no drain, 128 no in-cell stores, 256 no stores of the crossers' final positions, 512 one of the four."""
+32 no mover deposit, 64 no drain, 128 no in-cell stores, 256 no late stores of the crossers' final records (position and cell: one 16-byte store each)."""
 import argparse
 import importlib
 import os

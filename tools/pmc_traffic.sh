@@ -2,7 +2,8 @@
 # FETCH_SIZE and WRITE_SIZE are collected in separate --pmc passes (MI355X_MICROARCH.md: TCC has 4
 # slots, FETCH_SIZE takes 3, WRITE_SIZE 2), with --kernel-trace only.  Both are in KiB-like units of
 # 1024 B?? -> calibrated below on kernels of known traffic and the same access width (dword per lane):
-#   reads : sort_count_kernel      reads exactly 4 B per particle
+#   reads : sort_count_kernel      read exactly 4 B per particle while the cells were an array of their own (up to r04); it
+#           reads them at a 16-byte stride now (the position records: engine.h) and fetches whole records
 #   writes: load_maxwellian_kernel writes exactly 32 B per particle
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
