@@ -1052,10 +1052,10 @@ int vpic_hip_boundary_p_inject(vpic_hip_engine_t *e, const void *dev_injectors, 
 }
 
 int vpic_hip_face_count(const vpic_hip_engine_t *e, int dir) { return (e && dir >= 0 && dir < 6) ? k_face_count(e, dir) : 0; }
-int vpic_hip_pack_tang_b(vpic_hip_engine_t *e, int dir, void *buf) { ENGINE(e); return k_pack_face(e, dir, (float *)buf, 0); }
-int vpic_hip_unpack_tang_b(vpic_hip_engine_t *e, int dir, const void *buf) { ENGINE(e); return k_unpack_face(e, dir, (const float *)buf, 0); }
-int vpic_hip_pack_jf(vpic_hip_engine_t *e, int dir, void *buf) { ENGINE(e); return k_pack_face(e, dir, (float *)buf, 1); }
-int vpic_hip_unpack_jf(vpic_hip_engine_t *e, int dir, const void *buf) { ENGINE(e); return k_unpack_face(e, dir, (const float *)buf, 1); }
+int vpic_hip_pack_tang_b(vpic_hip_engine_t *e, int dir, void *buf) { ENGINE(e); if (dir < 0 || dir > 5 || !buf) VH_FAIL("Bad face message"); return k_pack_face(e, dir, (float *)buf, 0); }
+int vpic_hip_unpack_tang_b(vpic_hip_engine_t *e, int dir, const void *buf) { ENGINE(e); if (dir < 0 || dir > 5 || !buf) VH_FAIL("Bad face message"); return k_unpack_face(e, dir, (const float *)buf, 0); }
+int vpic_hip_pack_jf(vpic_hip_engine_t *e, int dir, void *buf) { ENGINE(e); if (dir < 0 || dir > 5 || !buf) VH_FAIL("Bad face message"); return k_pack_face(e, dir, (float *)buf, 1); }
+int vpic_hip_unpack_jf(vpic_hip_engine_t *e, int dir, const void *buf) { ENGINE(e); if (dir < 0 || dir > 5 || !buf) VH_FAIL("Bad face message"); return k_unpack_face(e, dir, (const float *)buf, 1); }
 
 // src/vpic/advance.cxx:38-214 for a domain that needs no other domain
 // The adaptive decision for one species (see vpic_hip_step; policy.h: sort_due): reads the event pairs k_advance_p and

@@ -817,6 +817,22 @@ class Engine:
     def unpack_rho(self, d, dev_ptr):
         self._ck(self._l.vpic_hip_unpack_rho(self._h, d, C.c_void_p(dev_ptr)))
 
+    # ... and of the hydro moments (sf_interface/hydro.c:28-200)
+    def local_adjust_hydro(self):
+        self._ck(self._l.vpic_hip_local_adjust_hydro(self._h))
+
+    def synchronize_hydro_self(self, axis):
+        self._ck(self._l.vpic_hip_synchronize_hydro_self(self._h, axis))
+
+    def hydro_count(self, d):
+        return self._l.vpic_hip_hydro_count(self._h, d)
+
+    def pack_hydro(self, d, dev_ptr):
+        self._ck(self._l.vpic_hip_pack_hydro(self._h, d, C.c_void_p(dev_ptr)))
+
+    def unpack_hydro(self, d, dev_ptr):
+        self._ck(self._l.vpic_hip_unpack_hydro(self._h, d, C.c_void_p(dev_ptr)))
+
     def message_count(self, kind, d):
         return self._l.vpic_hip_face_message_count(self._h, kind, d)
 

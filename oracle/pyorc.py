@@ -204,6 +204,34 @@ def synchronize_hydro_local(h, g):
     lib().orc_synchronize_hydro_local(_p(h), C.byref(g))
 
 
+def local_adjust_hydro(h, g):
+    lib().orc_local_adjust_hydro(_p(h), C.byref(g))
+
+
+def hydro_count(g, d):
+    return lib().orc_hydro_count(C.byref(g), d)
+
+
+def pack_hydro(h, g, d):
+    buf = np.zeros(hydro_count(g, d), np.float32)
+    lib().orc_pack_hydro(_p(buf), _p(h), C.byref(g), d)
+    return buf
+
+
+def unpack_hydro(h, buf, g, d):
+    lib().orc_unpack_hydro(_p(h), _p(np.ascontiguousarray(buf, np.float32)), C.byref(g), d)
+
+
+def synchronize_hydro_self(h, g, axis):
+    """One axis of synchronize_hydro for faces the domain shares with itself (hydro.c:28-163): both planes are packed
+    before either is added to."""
+    if g.fbc[axis] != g.rank or g.fbc[axis + 3] != g.rank:
+        return
+    lo, hi = pack_hydro(h, g, axis), pack_hydro(h, g, axis + 3)
+    unpack_hydro(h, lo, g, axis)
+    unpack_hydro(h, hi, g, axis + 3)
+
+
 def local_adjust_rho(f, g):
     lib().orc_local_adjust_rho(_p(f), C.byref(g))
 
