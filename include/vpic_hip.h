@@ -173,15 +173,41 @@ int vpic_hip_accumulate_rhob(vpic_hip_engine_t *e, const vpic_particle_t *p, int
  * such a face comes back at once with a momentum drawn from the flux of a Maxwellian at the wall -- normal
  * component sqrt(2) ut_para sqrt(-log U), tangential ones ut_perp N(0,1), per species -- and moves on for the
  * rest of its step.  Random numbers come from a counter-based generator on the device (seed, call, species,
- * mover): statistically the reference's handler, not its stream.  A face whose code has no parameters absorbs
- * (boundary_p.c:312-316). */
+ * mover): statistically the reference's handler, not its stream; its uniforms lie strictly inside (0, 1)
+ * (csrc/unit_draw.h), so the normal component is never exactly zero.  The faces a mover sits on are tried in the order
+ * -x -y -z +x +y +z; a face whose code has no parameters claims nothing and the next face is tried, and a mover that
+ * no face took is absorbed into rhob (boundary_p.c:268-277, :312-316).  Up to 4 codes; the same code again replaces
+ * its parameters. */
 int vpic_hip_set_maxwellian_reflux(vpic_hip_engine_t *e, int code, const float *ut_para, const float *ut_perp, int n_species, uint32_t seed);
 /* Parity tests: the three numbers the handler draws per refluxed particle (mt_frand, mt_frandn, mt_frandn:
  * maxwellian_reflux.c:120-122) from a table indexed by the particle's position in its species' array (3 floats each)
- * instead of the engine's counter-based generator; n_particles = 0 switches back. */
+ * instead of the engine's counter-based generator; n_particles = 0 switches back.  The arithmetic in this mode, float
+ * throughout, one rounding per operation (no contraction), d = the three draws of the particle's slot, h the handler:
+ *   u0 = (ut_para[h] * (+-sqrt2f)) * sqrtf(-logf(d[0]))     (- on the faces +x +y +z; sqrt2f the float nearest sqrt 2)
+ *   u1 = ut_perp[h] * d[1],  u2 = ut_perp[h] * d[2]          (u0 along the face's axis, u1 and u2 on the next two, cyclically)
+ *   dd = (g.dx * dispx, g.dy * dispy, g.dz * dispz),  r = (ux ux + uy uy) + uz uz of the OLD momentum
+ *   ratio = sqrtf(((1 + r) * ((ddx ddx + ddy ddy) + ddz ddz)) / ((1 + ((nux nux + nuy nuy) + nuz nuz)) * (FLT_MIN + r)))
+ *   new displacement = ((nux * ratio) * rdx, (nuy * ratio) * rdy, (nuz * ratio) * rdz); position, cell and charge are kept,
+ * and the injector finishes its move like an arrival (no tags).  Only logf is not correctly rounded: given u0, every
+ * other number is the same on any IEEE machine (oracle/vpic_oracle.h: orc_maxwellian_reflux_from_u). */
 int vpic_hip_set_reflux_draws(vpic_hip_engine_t *e, const float *draws, int64_t n_particles);
 /* The same for vpic_hip_emit: six numbers per emitted-particle slot (slot = component index * n_emit_per_face + k), in
- * the model's draw order (child-langmuir.c:60-75: mt_drand_c, mt_drand_c, mt_drandn x 3, mt_drand_c0). */
+ * the model's draw order (child-langmuir.c:60-75: mt_drand_c, mt_drand_c, mt_drandn x 3, mt_drand_c0).
+ * The arithmetic of a slot in this mode, d[0..5] its six double draws; X the face's axis, Y and Z the next two cyclically;
+ * dir = +1 on the faces -x -y -z (emission towards +X), -1 on +x +y +z; every operation rounded once, no contraction:
+ *   the face emits when (float) q_m * (dir * E_X) > 0 and |E_X| >= thresh_e_norm, E_X the interpolator's ex / ey / ez of the voxel
+ *   position on the face and momenta, from the double draws with ONE rounding each (as the reference has them):
+ *     pos_X = -dir, pos_Y = (float)(2 d[0] - 1), pos_Z = (float)(2 d[1] - 1)
+ *     u_X = (float)(dir * |(double)ut_para * d[2]|), u_Y = (float)((double)ut_perp * d[3]), u_Z = (float)((double)ut_perp * d[4])
+ *   the charge, in float with sqrtf, left to right:
+ *     q = ((((eps0 * d_Y) * d_Z) * dt) * sqrtf((coef * |((q_m * E_X) * E_X) * E_X|) / d_X)) / (float)n_emit_per_face, negated for q_m < 0
+ *   the age, in float:  age = (float)d[5];  age *= (cvac * dt) / sqrtf(((ux ux + uy uy) + uz uz) + 1)      (x, y, z order)
+ *   the displacements:  disp_k = (u_k * age) * rd_k,  k = x, y, z
+ *   rhob receives accumulate_rhob (boundary_p.c:9-71) of the position on the face with charge -q: w0 = (float)(0.125 *
+ *   (double)(-q) * (double)rdx * (double)rdy * (double)rdz) -- one double product, rounded once -- and the trilinear weights
+ *   from it in float, doubled on the domain's surface planes, added to the 8 nodes with float atomics (any order).
+ * The injector then finishes its move like an arrival.  The reference differs in the last bits of q and disp: it takes the
+ * root of the charge law and the age in double and divides by the cell size (DESIGN.md section 4 bounds the difference). */
 int vpic_hip_set_emit_draws(vpic_hip_engine_t *e, const double *draws, int64_t n_slots);
 /* n more particles at the end of the list (particles a deck injects while the run is under way,
  * vpic.hxx:463-486); pending movers keep their particle indices */

@@ -10,6 +10,7 @@
 // differs, the particle SET does not), and the counting sort hands out slots with atomics (order
 // within a voxel is not the stable order of sort_p.c:67; the partition is identical).
 #include "push_device.h"
+#include "unit_draw.h"
 #include <cstddef>
 #include <cstring>
 #include <algorithm>
@@ -115,7 +116,7 @@ __device__ __forceinline__ unsigned hash32(unsigned x) {
 }
 __device__ __forceinline__ float u01(unsigned seed, unsigned idx, unsigned k) {
   const unsigned h = hash32(hash32(idx * 9u + k) ^ hash32(seed * 0x9e3779b9u + k));
-  return ((h >> 8) + 0.5f) * (1.0f / 16777216.0f);     // (0,1)
+  return unit_top_closed(h);                           // (0, 1]: the loader keeps its draws (unit_draw.h)
 }
 __global__ __launch_bounds__(256)
 void load_maxwellian_kernel(ParticlesK p, GridK g, int ppc, int np, unsigned seed, float q,
@@ -792,9 +793,7 @@ struct RetryMover { vpic_particle_mover_t m; int sp, pad[3]; };                 
 // the reflux handlers as one species sees them (maxwellian_reflux.c:60-62)
 struct RefluxK { int n; int code[4]; float ut_para[4], ut_perp[4]; unsigned seed, call; const float *draws; int draws_n; };   // draws: test mode, see vpic_hip_set_reflux_draws
 
-// three uniforms in (0,1) from a counter: seed, call, species, mover (lowbias32 mixing)
-__device__ __forceinline__ unsigned mix32(unsigned x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; }
-__device__ __forceinline__ float unit_open(unsigned r) { return ((float)(r >> 8) + 0.5f) * (1.f / 16777216.f); }
+// three uniforms in (0,1) from a counter: seed, call, species, mover (mix32 and unit_open of unit_draw.h)
 
 // boundary_p.c:9-71 with atomics (several absorbed particles may share a node)
 __device__ __forceinline__ void accumulate_rhob_dev(float *rhob, float dx, float dy, float dz, float q, int pi,
@@ -879,7 +878,7 @@ void boundary_classify_kernel(ParticlesK p, const vpic_particle_mover_t *__restr
       // of the step is travelled with it: dr' = u' sqrt(((1+|u|^2)|dr|^2) / ((1+|u'|^2)|u|^2))
       int h = -1;
       for (int k = 0; k < rk.n; k++) if (rk.code[k] == code) h = k;
-      if (h < 0) break;                                    // no parameters: absorbed (boundary_p.c:312-316)
+      if (h < 0) continue;                                 // no such handler: on to the next face, absorbed only after the sixth (boundary_p.c:268-277, :312-316)
       float u[3];
       if (rk.draws && idx < rk.draws_n) {
         // test mode: the handler's three draws (uniform, normal, normal: maxwellian_reflux.c:120-122) come from a

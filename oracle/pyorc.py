@@ -345,6 +345,47 @@ def maxwellian_reflux(draws, p, pm, g, ut_para, ut_perp, face, sp_id=0):
     return out[0]
 
 
+def maxwellian_reflux_draw(draws, ut_para, ut_perp, face):
+    """orc_maxwellian_reflux_draw: (u normal to the face, the two tangential ones) of one handler call, float32[3]"""
+    u = np.zeros(3, np.float32)
+    d = np.ascontiguousarray(draws, np.float32)
+    lib().orc_maxwellian_reflux_draw(_p(d), C.c_float(ut_para), C.c_float(ut_perp), int(face), _p(u))
+    return u
+
+
+def maxwellian_reflux_from_u(u, p, pm, g, sp_id=0):
+    """orc_maxwellian_reflux_from_u for mover record pm (one element) of particle array p with the new momentum
+    u = (ux, uy, uz) in the grid's axes; returns the injector record."""
+    out = np.zeros(1, L.particle_injector_t)
+    part = p[int(pm["i"][0]):int(pm["i"][0]) + 1]
+    lib().orc_maxwellian_reflux_from_u(C.c_float(u[0]), C.c_float(u[1]), C.c_float(u[2]), _p(part), _p(pm), C.byref(g), int(sp_id), _p(out))
+    return out[0]
+
+
+def boundary_p_reflux_round(p, pm, sp_id, f, a, g, handlers, draws, u_normal=None):
+    """orc_boundary_p_reflux_round on copies: p the species' particles in array order, pm its movers, handlers a list of
+    (code, ut_para, ut_perp) for THIS species, draws float32[n, 3] indexed by array slot, u_normal None or float32[len(pm)].
+    rhob is added to f and the deposits to a (in place).  Returns (particles after the round: survivors, then the
+    refluxed ones; new movers; injectors; the index in pm of the mover behind each injector; the face whose handler made it)."""
+    nm = len(pm)
+    out = np.zeros(len(p) + 1, L.particle_t)
+    out[:len(p)] = p
+    mv = np.zeros(max(nm, 1), L.particle_mover_t)
+    mv[:nm] = pm
+    codes = np.array([h[0] for h in handlers], np.int32)
+    para = np.array([h[1] for h in handlers], np.float32)
+    perp = np.array([h[2] for h in handlers], np.float32)
+    d = np.ascontiguousarray(draws, np.float32).reshape(-1, 3)
+    un = None if u_normal is None else np.ascontiguousarray(u_normal, np.float32)
+    assert un is None or len(un) == nm
+    inj, who, face = np.zeros(max(nm, 1), L.particle_injector_t), np.zeros(max(nm, 1), np.int32), np.zeros(max(nm, 1), np.int32)
+    nm_c, ni_c = C.c_int(nm), C.c_int(0)
+    new_np = lib().orc_boundary_p_reflux_round(_p(out), len(p), _p(mv), C.byref(nm_c), int(sp_id), _p(f), _p(a), C.byref(g),
+                                               _p(codes), _p(para), _p(perp), len(codes), _p(d), len(d),
+                                               None if un is None else _p(un), _p(inj), _p(who), _p(face), C.byref(ni_c))
+    return out[:new_np], mv[:nm_c.value], inj[:ni_c.value], who[:ni_c.value], face[:ni_c.value]
+
+
 def child_langmuir(p, np_, pm, nm, component, n_emit, ut_perp, ut_para, q_m, fi, f, a, g, draws):
     """orc_child_langmuir; returns (new np, new nm)."""
     nm_c = C.c_int(nm)

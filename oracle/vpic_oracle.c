@@ -835,17 +835,21 @@ int orc_boundary_p_inject(orc_particle_t *p0, int np, orc_mover_t *pm0, int *nm_
  * re-emitted with the momentum of the flux of a Maxwellian at the wall and travels what is left of the step with it.
  * The three random numbers the handler draws -- mt_frand (uniform on (0,1)), then two mt_frandn (normals) -- are
  * passed in, in that order, so that the restatement can be checked particle by particle against the reference's
- * own handler fed from a generator in the same state (oracle/gen_reflux.py).  face: 0..5 = -x,-y,-z,+x,+y,+z.   */
-void orc_maxwellian_reflux(const float draws[3], const orc_particle_t *r, const orc_mover_t *pm,
-                           const orc_grid_t *g, float ut_para, float ut_perp, int face, int sp_id,
-                           orc_injector_t *pi) {
-  static const int perm[6][3] = {{0, 1, 2}, {2, 0, 1}, {1, 2, 0}, {0, 1, 2}, {2, 0, 1}, {1, 2, 0}};   /* :70-75 */
+ * own handler fed from a generator in the same state (oracle/gen_reflux.py).  face: 0..5 = -x,-y,-z,+x,+y,+z.
+ * In two halves: the draw (:120-122, u[0] normal to the face, u[1], u[2] tangential) and everything after it.       */
+static const int reflux_perm[6][3] = {{0, 1, 2}, {2, 0, 1}, {1, 2, 0}, {0, 1, 2}, {2, 0, 1}, {1, 2, 0}};   /* :70-75 */
+void orc_maxwellian_reflux_draw(const float draws[3], float ut_para, float ut_perp, int face, float u[3]) {
   static const float scale[6] = {M_SQRT2, M_SQRT2, M_SQRT2, -M_SQRT2, -M_SQRT2, -M_SQRT2};           /* :76-77 */
-  float u[3], ux, uy, uz, dispx, dispy, dispz, ratio;
   u[0] = ut_para * scale[face] * sqrtf(-logf(draws[0]));                                              /* :120 */
   u[1] = ut_perp * draws[1];
   u[2] = ut_perp * draws[2];
-  ux = u[perm[face][0]]; uy = u[perm[face][1]]; uz = u[perm[face][2]];
+}
+
+/* :124-175 -- from the new momentum (ux, uy, uz) (already in the grid's axes), the old particle and its mover to the
+ * injector: the rest of the step is travelled with the new momentum.  Only + - * / sqrtf: exact on every side.    */
+void orc_maxwellian_reflux_from_u(float ux, float uy, float uz, const orc_particle_t *r, const orc_mover_t *pm,
+                                  const orc_grid_t *g, int sp_id, orc_injector_t *pi) {
+  float dispx, dispy, dispz, ratio;
   dispx = g->dx * pm->dispx; dispy = g->dy * pm->dispy; dispz = g->dz * pm->dispz;                     /* :146-148 */
   ratio = r->ux * r->ux + r->uy * r->uy + r->uz * r->uz;
   ratio = sqrtf(((1 + ratio) * (dispx * dispx + dispy * dispy + dispz * dispz)) /
@@ -854,6 +858,91 @@ void orc_maxwellian_reflux(const float draws[3], const orc_particle_t *r, const 
   pi->dx = r->dx; pi->dy = r->dy; pi->dz = r->dz; pi->i = r->i;                                         /* :163-174 */
   pi->ux = ux; pi->uy = uy; pi->uz = uz; pi->q = r->q;
   pi->dispx = dispx; pi->dispy = dispy; pi->dispz = dispz; pi->sp_id = sp_id;
+}
+
+void orc_maxwellian_reflux(const float draws[3], const orc_particle_t *r, const orc_mover_t *pm,
+                           const orc_grid_t *g, float ut_para, float ut_perp, int face, int sp_id,
+                           orc_injector_t *pi) {
+  float u[3];
+  orc_maxwellian_reflux_draw(draws, ut_para, ut_perp, face, u);
+  orc_maxwellian_reflux_from_u(u[reflux_perm[face][0]], u[reflux_perm[face][1]], u[reflux_perm[face][2]], r, pm, g, sp_id, pi);
+}
+
+/* One round of boundary_p for one species of ONE domain with handlers: boundary_p.c:194-320 (classify) and :457-497
+ * (inject what the handlers made).  Per mover, the faces in the reference's order 0..5; at a face the particle sits on
+ * and leaves through: absorb -> rhob; a handler code (<= -3) that is among h_code[0 .. n_handler) -> maxwellian_reflux
+ * with that handler's (ut_para, ut_perp), injector appended; ANYTHING ELSE -- reflect, this same domain, a handler code
+ * registered nowhere -- falls through to the next face (:268-277), and a mover no face took is absorbed (:312-316).  A
+ * face shared with another domain has no place here (DIE).
+ * The handler's draws come from a table indexed by the particle's position in its array, draws[3 * pm->i ..] (the
+ * engine's test-mode rule, vpic_hip_set_reflux_draws); u_normal, when not NULL, holds per mover (index into pm0) the
+ * new momentum normal to the face to use in place of line :120 (its sign included).
+ * The movers are taken in descending order of the slot they name (the reference's own lists ascend and are walked last
+ * to first; with that order the back-fill r[0] = p0[--np] never moves a particle whose mover is still to come), ties
+ * in list order last to first.
+ * Out: inj[0 .. *n_inj) in the order the handlers made them, inj_mover[k] = the index in pm0 of the mover that made
+ * inj[k] and inj_face[k] = the face whose handler did (all three of capacity nm); p0 holds the survivors and then the injected particles (capacity np: a mover removes
+ * one and adds at most one); pm0[0 .. *nm_io) the new movers; rhob in f; the accumulator (and the fixed-point one,
+ * orc_set_fixed_accumulator) in a0.  Returns the new np.                                                           */
+typedef struct { int32_t slot, k; } rr_key_t;                        /* (the slot a mover names, its index in the list) */
+static int rr_cmp(const void *a, const void *b) {
+  const rr_key_t *x = (const rr_key_t *)a, *y = (const rr_key_t *)b;
+  if (x->slot != y->slot) return x->slot < y->slot ? -1 : 1;
+  return x->k < y->k ? -1 : x->k > y->k;
+}
+int orc_boundary_p_reflux_round(orc_particle_t *p0, int np, orc_mover_t *pm0, int *nm_io, int sp_id,
+                                orc_field_t *f, orc_accumulator_t *a0, const orc_grid_t *g,
+                                const int *h_code, const float *h_ut_para, const float *h_ut_perp, int n_handler,
+                                const float *draws, int n_draws, const float *u_normal,
+                                orc_injector_t *inj, int *inj_mover, int *inj_face, int *n_inj) {
+  const int nm = *nm_io;
+  int ni = 0;
+  rr_key_t *order = (rr_key_t *)malloc(sizeof(rr_key_t) * (size_t)(nm > 0 ? nm : 1));
+  if (!order) DIE("out of memory");
+  for (int k = 0; k < nm; k++) { order[k].slot = pm0[k].i; order[k].k = k; }
+  qsort(order, (size_t)nm, sizeof(rr_key_t), rr_cmp);
+  for (int o = nm - 1; o >= 0; o--) {
+    const int k = order[o].k;
+    const orc_mover_t *pm = pm0 + k;
+    if (pm->i < 0 || pm->i >= np) DIE("a mover names no particle");
+    orc_particle_t *r = p0 + pm->i;
+    const float d[3] = {r->dx, r->dy, r->dz}, u[3] = {r->ux, r->uy, r->uz};
+    int handled = 0;
+    for (int face = 0; face < 6 && !handled; face++) {
+      const int axis = face % 3, hi = face >= 3;
+      const int cond = hi ? ((d[axis] == 1) & (u[axis] > 0)) : ((d[axis] == -1) & (u[axis] < 0));        /* :304-309 */
+      if (!cond) continue;
+      const int code = g->pbc[face];
+      if (code == ORC_ABSORB_PARTICLES) {                                                               /* :243-247 */
+        orc_accumulate_rhob(f, r, g);
+        handled = 1;
+      } else if (code >= 0 && code != g->rank) {
+        DIE("orc_boundary_p_reflux_round: a face shared with another domain");
+      } else if (code < ORC_ABSORB_PARTICLES) {                                                         /* :271-277 */
+        int h = -1;
+        for (int j = 0; j < n_handler; j++) if (h_code[j] == code) h = j;
+        if (h < 0) continue;                                 /* registered nowhere: falls through to the next face */
+        if (pm->i >= n_draws) DIE("orc_boundary_p_reflux_round: no draws for a refluxed particle");
+        float v[3];
+        orc_maxwellian_reflux_draw(draws + 3 * (size_t)pm->i, h_ut_para[h], h_ut_perp[h], face, v);
+        if (u_normal) v[0] = u_normal[k];
+        orc_maxwellian_reflux_from_u(v[reflux_perm[face][0]], v[reflux_perm[face][1]], v[reflux_perm[face][2]], r, pm, g, sp_id,
+                                     inj + ni);
+        inj_face[ni] = face;
+        inj_mover[ni++] = k;
+        handled = 1;
+      }
+    }
+    if (!handled) orc_accumulate_rhob(f, r, g);       /* :312-316 "Unknown boundary interaction ... using absorption" */
+    r[0] = p0[--np];
+  }
+  free(order);
+  int nm_new = 0;
+  for (int k = 0; k < ni; k++) p0[np + k].tag = p0[np + k].tag2 = 0;   /* an injector record has no tag fields */
+  np = orc_boundary_p_inject(p0, np, pm0, &nm_new, inj, ni, a0, g);
+  *nm_io = nm_new;
+  *n_inj = ni;
+  return np;
 }
 
 /* emitter/child-langmuir.c:15-120 -- the surface emission model: every listed cell face whose normal field pulls the

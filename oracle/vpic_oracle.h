@@ -157,6 +157,26 @@ int  orc_boundary_p_inject(orc_particle_t *p0, int np, orc_mover_t *pm, int *nm,
 void orc_maxwellian_reflux(const float draws[3], const orc_particle_t *r, const orc_mover_t *pm,
                            const orc_grid_t *g, float ut_para, float ut_perp, int face, int sp_id,
                            orc_injector_t *pi);
+/* ... in its two halves.  The draw (:120-122): u[0] = ut_para * (+-sqrt 2) * sqrtf(-logf(draws[0])) normal to the face,
+ * u[1], u[2] = ut_perp * draws[1], [2] tangential (the handler's own order, before its perm[][]).  And everything after
+ * it (:124-175): from the new momentum in the grid's axes, the old particle and its mover to the injector -- + - * /
+ * sqrtf only, so a new momentum computed elsewhere (a device with another logf) gives the same injector everywhere. */
+void orc_maxwellian_reflux_draw(const float draws[3], float ut_para, float ut_perp, int face, float u[3]);
+void orc_maxwellian_reflux_from_u(float ux, float uy, float uz, const orc_particle_t *r, const orc_mover_t *pm,
+                                  const orc_grid_t *g, int sp_id, orc_injector_t *pi);
+/* One round of boundary_p (boundary_p.c:194-320, then :457-497) for one species of one domain with up to four handlers
+ * (code, ut_para, ut_perp): the reference's face order, fall-through at a face nothing claims (reflect, this same domain,
+ * a handler code registered nowhere), absorption into rhob, handler, injection through orc_boundary_p_inject (so the
+ * fixed-point switch sees it).  draws[3 * slot ..]: the handler's draws of the particle in array slot `slot` (n_draws
+ * slots); u_normal: NULL, or per mover the new normal momentum to use in place of :120.  See vpic_oracle.c.
+ * Out: inj / inj_mover / inj_face (capacity *nm each, *n_inj made: the injector, the mover behind it, the face whose
+ * handler made it), the survivors and then the injected particles in p0, the new
+ * movers in pm0 and *nm.  Returns the new np. */
+int  orc_boundary_p_reflux_round(orc_particle_t *p0, int np, orc_mover_t *pm0, int *nm, int sp_id,
+                                 orc_field_t *f, orc_accumulator_t *a0, const orc_grid_t *g,
+                                 const int *h_code, const float *h_ut_para, const float *h_ut_perp, int n_handler,
+                                 const float *draws, int n_draws, const float *u_normal,
+                                 orc_injector_t *inj, int *inj_mover, int *inj_face, int *n_inj);
 
 /* emitter/child-langmuir.c:15-120 with the model's six draws per emitted particle passed in (see vpic_oracle.c) */
 int orc_child_langmuir(orc_particle_t *p0, int np, int max_np, orc_mover_t *pm0, int *nm_io, int max_nm,

@@ -9,9 +9,10 @@ is exact: accumulators as uint32 words, ghosts included; particles and movers by
 
 Instances (policy.h: PushInstance): det_tile (tile order by cell), det_tile_only (VPIC_HIP_TILE_COARSE=1, fresh child),
 det_row (the reference's order: asked for, or kept on grids thinner than a tile), and the windowless fixed-point deposits
-of injection.  Not covered: emission (vpic_hip_emit) -- the device takes the square root of the charge law in float, the
-oracle in double (test_gpu_kernels.py::test_child_langmuir_emitter_particle_by_particle), so the emitted charges differ
-in the last bit and with them every deposit: there is no exact reference to hold it to."""
+of injection.  Emission (vpic_hip_emit) and the reflux walls are held exactly elsewhere: the device takes the square root
+of the emitter's charge law in float, the oracle in double, so the oracle is no exact reference for it -- the numpy
+restatement of the arithmetic include/vpic_hip.h states is (tests/source_ref.py, tests/test_gpu_emit.py), and
+tests/test_gpu_reflux.py holds every round of boundary_p with Maxwellian reflux handlers to the oracle."""
 import os
 import sys
 

@@ -297,6 +297,66 @@ def test_maxwellian_reflux_restatement_against_the_references_handler(orc, L):
             assert np.asarray(out[c]).view(np.uint32) == np.asarray(ref[c]).view(np.uint32), (k, c)
 
 
+def test_maxwellian_reflux_in_two_halves_is_the_whole(orc, L):
+    """orc_maxwellian_reflux_draw, the handler's perm[][], then orc_maxwellian_reflux_from_u: the injector of the whole
+    handler, bit for bit, on every call of the fixture (which pins the whole on the reference, above)."""
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reflux.npz"))
+    og = orc.make_grid(*[int(v) for v in g["dims"]], *[float(v) for v in g["box"][:3]], np.float32(g["box"][3]))
+    perm = [(0, 1, 2), (2, 0, 1), (1, 2, 0)] * 2
+    for k in range(len(g["p"])):
+        face = int(g["face"][k])
+        u = orc.maxwellian_reflux_draw(g["draws"][k], float(g["ut"][0]), float(g["ut"][1]), face)
+        assert (u[0] < 0) == (face >= 3) and u[0] != 0
+        out = orc.maxwellian_reflux_from_u(u[list(perm[face])], g["p"], g["pm"][k:k + 1], og)
+        assert bits_equal(np.array([out]), g["inj"][k:k + 1]), k
+
+
+@pytest.mark.parametrize("world", ["handlers", "mixed"])
+def test_reflux_round_against_the_references_boundary_p(orc, L, world):
+    """tests/golden/reflux_round.npz (oracle/gen_reflux_round.py): the reference's own boundary_p on a 6 x 5 x 4 domain with
+    maxwellian_reflux registered under two codes, a third code registered nowhere and (world "mixed") absorbing,
+    reflecting and self-periodic faces; movers on every face, on every pair of faces and in the corners.
+    orc_boundary_p_reflux_round fed the numbers the handler drew leaves the same world, bit for bit: the survivors (a
+    multiset: by charge), the refluxed particles in the reference's order, the movers they left, rhob, the accumulator."""
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reflux_round.npz"))
+    G = {k[len(world) + 1:]: g[k] for k in g.files if k.startswith(world + "_")}
+    og = orc.make_grid(*[int(v) for v in g["dims"]], *[float(v) for v in g["box"][:3]], np.float32(g["box"][3]),
+                       fbc=[L.PEC_FIELDS] * 6, pbc=[int(c) for c in G["pbc"]])
+    handlers = [(int(c), float(a), float(b)) for c, a, b in g["handlers"]]
+    f, a = np.zeros(og.nv, L.field_t), np.zeros(og.nv, L.accumulator_t)
+    p, pm, inj, who, face = orc.boundary_p_reflux_round(G["p"], G["pm"], 0, f, a, og, handlers, G["draws"])
+    n_inj, ref = int(G["n_inj"]), G["out_p"]
+    n_keep = len(ref) - n_inj
+    assert len(inj) == n_inj and len(p) == len(ref) and len(pm) == len(G["out_pm"])
+    assert 0 < n_inj < len(G["pm"]) and len(pm) > 0                    # some refluxed, some absorbed, some stopped on a face again
+    by_q = lambda x: x[np.argsort(x["q"], kind="stable")]
+    assert bits_equal(by_q(p[:n_keep]), by_q(ref[:n_keep]))
+    assert bits_equal(p[n_keep:], ref[n_keep:])
+    assert bits_equal(pm, G["out_pm"])
+    assert bits_equal(f["rhob"], G["rhob"]) and np.abs(G["rhob"]).sum() > 0
+    assert bits_equal(a, G["a"]) and np.abs(G["a"]["jx"]).sum() > 0
+    # who made which injector: the movers walked last to first, and the injected tail is the injectors reversed
+    assert np.all(np.diff(who) < 0)
+    assert bits_equal(inj["q"][::-1], ref["q"][n_keep:]) and bits_equal(G["p"]["q"][G["pm"]["i"][who]], inj["q"])
+    # the fall-through decided something: movers whose FIRST face carries the unregistered code, a reflecting or a
+    # self-periodic wall and that a handler took at a later face (boundary_p.c:268-277) -- the refluxed movers are those
+    # the face order says, no more and no fewer
+    codes, registered = G["pbc"], {h[0] for h in handlers}
+
+    def fate(faces):
+        for face in faces[faces >= 0]:                                  # (ascending: TEST_FACE 0 .. 5)
+            if codes[face] == L.ABSORB_PARTICLES:
+                return "absorb"
+            if codes[face] in registered:
+                return "reflux"
+        return "absorb"
+    fates = np.array([fate(fs) for fs in G["faces"]])
+    assert all(f in G["faces"][k] and codes[f] in registered for k, f in zip(who, face))
+    assert set(np.flatnonzero(fates == "reflux")) == set(who)
+    fell = (fates == "reflux") & ~np.isin(codes[G["faces"][:, 0]], list(registered))
+    assert fell.sum() >= 4
+
+
 def test_child_langmuir_restatement_against_the_references_model(orc, L):
     """tests/golden/reflux.npz, emit_*: the reference's own child_langmuir (emitter.h) on 72 faces of all six
     orientations (+ a cell body) in a random interpolator, with the six numbers each emitted particle drew.  The
