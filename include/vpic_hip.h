@@ -177,7 +177,7 @@ int vpic_hip_accumulate_rhob(vpic_hip_engine_t *e, const vpic_particle_t *p, int
  * (csrc/unit_draw.h), so the normal component is never exactly zero.  The faces a mover sits on are tried in the order
  * -x -y -z +x +y +z; a face whose code has no parameters claims nothing and the next face is tried, and a mover that
  * no face took is absorbed into rhob (boundary_p.c:268-277, :312-316).  Up to 4 codes; the same code again replaces
- * its parameters. */
+ * its parameters.  A code that is a wall (vpic_hip_set_wall, below) is refused. */
 int vpic_hip_set_maxwellian_reflux(vpic_hip_engine_t *e, int code, const float *ut_para, const float *ut_perp, int n_species, uint32_t seed);
 /* Parity tests: the three numbers the handler draws per refluxed particle (mt_frand, mt_frandn, mt_frandn:
  * maxwellian_reflux.c:120-122) from a table indexed by the particle's position in its species' array (3 floats each)
@@ -191,6 +191,55 @@ int vpic_hip_set_maxwellian_reflux(vpic_hip_engine_t *e, int code, const float *
  * and the injector finishes its move like an arrival (no tags).  Only logf is not correctly rounded: given u0, every
  * other number is the same on any IEEE machine (oracle/vpic_oracle.h: orc_maxwellian_reflux_from_u). */
 int vpic_hip_set_reflux_draws(vpic_hip_engine_t *e, const float *draws, int64_t n_particles);
+/* ABSORBING WALLS THAT TALLY AND RECORD what they take (the reference's absorb_tally and link_boundary handlers,
+ * src/boundary/absorb_tally.c and link.c, and the same for the plain absorbing faces).
+ * A WALL is a particle boundary code registered with vpic_hip_set_wall: VPIC_ABSORB_PARTICLES itself (the plain absorbing
+ * faces are tallied) or a code <= -3 (what add_boundary returns).  At most 4 codes are walls, and a code is never a wall
+ * and a maxwellian_reflux handler at once.
+ * Who is absorbed where.  Every mover is looked at once per round (vpic_hip_boundary_p_pack, vpic_hip_exchange_pack*), the
+ * faces f = 0..5 (-x -y -z +x +y +z) in turn.  Face f is MET when the stored position component on its axis is exactly -1
+ * (f < 3) or +1 (f >= 3) and the momentum component on that axis is < 0 or > 0 respectively (boundary_p.c:304-309).  At the
+ * first met face whose code is a wall or VPIC_ABSORB_PARTICLES the mover is absorbed AT THAT FACE.  Every other code behaves
+ * as without walls: a face shared with another domain sends, a registered reflux code refluxes, and a reflecting face, a
+ * face of this same domain or a code <= -3 registered nowhere pass the mover on to the next face.  A mover that no face took
+ * is absorbed at face 6, "none".  Absorption itself is what it is without walls: accumulate_rhob, then removal (on the
+ * device-resident exchange: a dead slot).
+ * Tallies.  One table [7][n_species] of vpic_hip_wall_tally_t.  Row f < 6 takes the particles absorbed at face f when that
+ * face's code is a wall; row 6 takes EVERY OTHER particle absorbed while at least one wall is registered (plain absorbing
+ * faces that are not registered, and face "none"): the rows together account for every absorption.  Per absorbed particle,
+ * in IEEE double, every operation rounded once and unfused:
+ *   count += 1
+ *   val0 = (double)q
+ *   val1 = (double)q * ke,   ke = sqrt(((1 + ux ux) + uy uy) + uz uz) - 1    (VPIC_HIP_COORD_KE's expression)
+ *   for k = 0, 1:  t = val_k / quantum_k;  fabs(t) < 4294967296.0 ?  isum[k] += llrint(t)  :  refused[k] += 1
+ * (a NaN is refused; a refused particle is still counted and still absorbed) -- the rule of
+ * vpic_hip_species_distribution_sums word for word.  The sums are integers: the same bits in any mover order, on either
+ * exchange path, and additive across domains.  The caller reads and clears them; nothing else does.  |llrint(t)| < 2^32,
+ * so a table left running for more than 2^31 absorptions in one row can wrap its 64-bit sums.
+ * Records.  One device buffer of record_cap vpic_hip_wall_record_t.  A particle absorbed at a face whose wall was
+ * registered with VPIC_HIP_WALL_RECORD is appended as it is stored at that moment (offsets, voxel, momenta, charge), with
+ * its two tags (0 for a species without tags), the face and the species index.  A record that does not fit is dropped and
+ * counted in `dropped`; the tally still takes the particle, and nothing is written past the buffer.  Records of an earlier
+ * call precede those of a later one; the order within a call is unspecified. */
+typedef struct vpic_hip_wall_tally { int64_t count; int64_t isum[2]; int64_t refused[2]; } vpic_hip_wall_tally_t;
+typedef struct vpic_hip_wall_record { float dx, dy, dz; int32_t i; float ux, uy, uz, q; int64_t tag, tag2; int32_t face, sp; } vpic_hip_wall_record_t;
+VPIC_HIP_STATIC_ASSERT(sizeof(vpic_hip_wall_tally_t) == 40, "a wall tally is five 64-bit words");
+VPIC_HIP_STATIC_ASSERT(sizeof(vpic_hip_wall_record_t) == 56, "a wall record is 56 bytes");
+enum { VPIC_HIP_WALL_TALLY = 1, VPIC_HIP_WALL_RECORD = 2 };
+enum { VPIC_HIP_WALL_ROWS = 7, VPIC_HIP_WALL_MAX = 4 };
+/* (Re)allocates the tally table and the record buffer and zeroes both (the registered walls stay).  quantum_q and
+ * quantum_qke: the quanta of isum[0] and isum[1], positive and finite; record_cap >= 0, 0: no record buffer. */
+int vpic_hip_wall_setup(vpic_hip_engine_t *e, double quantum_q, double quantum_qke, int64_t record_cap);
+/* Makes `code` a wall (flags: VPIC_HIP_WALL_TALLY, VPIC_HIP_WALL_RECORD, which implies TALLY), replaces the flags of a
+ * code that already is one, or with flags 0 unregisters it.  Refused: a code that is not VPIC_ABSORB_PARTICLES or <= -3,
+ * a code that is a maxwellian_reflux handler, a fifth code, unknown flag bits, a call before vpic_hip_wall_setup. */
+int vpic_hip_set_wall(vpic_hip_engine_t *e, int code, int flags);
+/* out[7 * n_species], as out[row * n_species + sp]; n_species >= the engine's species count (the columns beyond it are
+ * zero).  clear != 0: the table restarts at zero. */
+int vpic_hip_wall_tally(vpic_hip_engine_t *e, vpic_hip_wall_tally_t *out, int n_species, int clear);
+/* Copies up to `cap` records in buffer order into out (may be NULL when cap is 0); *n: how many were copied, *dropped:
+ * how many did not fit into the device buffer since it was last cleared.  clear != 0: the cursor and `dropped` restart. */
+int vpic_hip_wall_records(vpic_hip_engine_t *e, vpic_hip_wall_record_t *out, int64_t cap, int64_t *n, int64_t *dropped, int clear);
 /* The same for vpic_hip_emit: six numbers per emitted-particle slot (slot = component index * n_emit_per_face + k), in
  * the model's draw order (child-langmuir.c:60-75: mt_drand_c, mt_drand_c, mt_drandn x 3, mt_drand_c0).
  * The arithmetic of a slot in this mode, d[0..5] its six double draws; X the face's axis, Y and Z the next two cyclically;
@@ -790,7 +839,9 @@ int vpic_hip_boundary_p_pack(vpic_hip_engine_t *e);
  *   message was full -- in both cases the movers concerned are still on their lists (_species_nm > 0) and the caller offers
  *   them again with larger messages (the header's `wanted` > `count` tells both ends of a message); a species out of
  *   particle or mover slots is an error (reserve earlier: _species_reserve).
- * Faces that belong to no other domain behave as in _boundary_p_pack; custom handlers (reflux) are not served. */
+ * Faces that belong to no other domain behave as in _boundary_p_pack, absorbing walls that tally and record
+ * (vpic_hip_set_wall) included; maxwellian_reflux handlers are not served (they create local injectors): _exchange_pack
+ * refuses an engine that has one. */
 int vpic_hip_advance_p_async(vpic_hip_engine_t *e, int sp);
 /* The overlap of the exchange with the push (north star; the reference's begin / interior / end pattern,
  * field_advance/standard/advance_e.c:114,153,191-197, applied to boundary_p.c:341-384).  A species in the engine's tile

@@ -22,6 +22,12 @@
 extern "C" {
 #endif
 
+/* boundary_t (src/grid/grid.h:43-53): a custom particle boundary handler and the copy of its parameters */
+typedef struct vpic_boundary {
+  void (*handler)(void);          /* (the reference's handlers take ten arguments; here a handler is only a name) */
+  char params[1024];              /* MAX_BOUNDARY_DATA_SIZE */
+} vpic_boundary_t;
+
 /* grid_t, byte for byte (src/grid/grid.h:112-167; sizeof 240, offsets pinned below) */
 typedef struct vpic_grid {
   void *mp;                       /* mp_handle */
@@ -34,7 +40,7 @@ typedef struct vpic_grid {
   int64_t *neighbor;              /* 6*nv: -x,-y,-z,+x,+y,+z neighbours, or particle bc codes */
   int64_t rangel, rangeh;
   int32_t nb;
-  void *boundary;
+  vpic_boundary_t *boundary;      /* nb of them; handler k answers to particle code -(k + 3) */
 } vpic_grid_t;
 VPIC_HIP_STATIC_ASSERT(sizeof(vpic_grid_t) == 240 && offsetof(vpic_grid_t, dt) == 8 &&
                        offsetof(vpic_grid_t, x0) == 24 && offsetof(vpic_grid_t, dx) == 48 &&

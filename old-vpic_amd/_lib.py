@@ -116,6 +116,11 @@ def lib():
         L.vpic_hip_set_collide_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     if hasattr(L, "vpic_hip_collide_relativistic"):         # (... or has them without the relativistic pair)
         L.vpic_hip_collide_relativistic.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(L, "vpic_hip_wall_setup"):                   # (an older build under VPIC_HIP_LIB has no walls: tools/wall_time.py times one)
+        L.vpic_hip_wall_setup.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int64]
+        L.vpic_hip_set_wall.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.vpic_hip_wall_tally.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.vpic_hip_wall_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
     L.vpic_hip_dump_gather.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_size_t]
     _lib = L
     return L
@@ -139,4 +144,5 @@ vpic_hip_species_distribution_sums vpic_hip_species_distribution_sums_stats
 vpic_hip_cell_distribution vpic_hip_cell_distribution_stats
 vpic_hip_species_select_count vpic_hip_species_select vpic_hip_species_select_stats
 vpic_hip_accumulate_hydro_p_select
+vpic_hip_wall_setup vpic_hip_set_wall vpic_hip_wall_tally vpic_hip_wall_records
 vpic_hip_collide vpic_hip_collide_relativistic vpic_hip_collide_stats vpic_hip_collide_instance vpic_hip_set_collide_draws""".split()

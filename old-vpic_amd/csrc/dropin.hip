@@ -73,7 +73,8 @@ vpic_hip_grid_t describe(const vpic_grid_t *g) {
     }
     (void)first;
     if (code == -1000) DIE("face %d leads to another domain but bc[] names none", face);
-    if (code < VPIC_ABSORB_PARTICLES) DIE("custom particle boundary handlers are not supported on the HIP path");
+    // (a code <= -3 names a custom particle boundary handler: only boundary_p would call one, and its twin refuses such a
+    // grid itself; center_p, energy_p, the field twins ... of a deck that has handlers never look at the code)
     d.pbc[face] = code;
   }
   return d;

@@ -360,6 +360,15 @@ struct Engine {
   uint32_t reflux_seed = 0; uint32_t reflux_calls = 0;
   float *reflux_draws = nullptr; int64_t reflux_draws_n = 0;
   double *emit_draws = nullptr; int64_t emit_draws_n = 0;      // test mode: the emission model's draws per emitted-particle slot   // test mode: the handlers' draws per particle index
+  // absorbing walls that tally and record (vpic_hip_wall_*): the registered codes, the quanta of the two sums, the table
+  // [VPIC_HIP_WALL_ROWS][MAX_SPECIES] and the record buffer with its cursor {records wanted since the last clear}
+  struct Wall { int code, flags; };
+  std::vector<Wall> walls;
+  bool wall_ready = false;                                     // vpic_hip_wall_setup has run
+  double wall_quantum[2] = {0, 0};
+  vpic_hip_wall_tally_t *wall_table = nullptr;
+  vpic_hip_wall_record_t *wall_rec = nullptr; int64_t wall_rec_cap = 0;
+  unsigned long long *wall_cursor = nullptr;
   vpic_particle_injector_t *local_buf = nullptr; int64_t local_cap = 0;   // injectors that re-enter this same domain
   int32_t send_count[6] = {};
   int *hole_list = nullptr, *fill_list = nullptr, *tail_flag = nullptr; int64_t list_cap = 0;

@@ -190,6 +190,7 @@ static void destroy(Engine *e) {
   (void)hipFree(e->face_buf[0]); (void)hipFree(e->face_buf[1]);
   for (int f = 0; f < 6; f++) (void)hipFree(e->send_buf[f]);
   (void)hipFree(e->local_buf); (void)hipFree(e->reflux_draws); (void)hipFree(e->emit_draws);
+  (void)hipFree(e->wall_table); (void)hipFree(e->wall_rec); (void)hipFree(e->wall_cursor);
   (void)hipFree(e->collide_draws); (void)hipFree(e->collide_dev); (void)hipHostFree(e->collide_host);
   (void)hipFree(e->hole_list); (void)hipFree(e->fill_list); (void)hipFree(e->tail_flag);
   (void)hipFree(e->sp_table_dev); (void)hipHostFree(e->sp_table_host); (void)hipFree(e->xmsg_dev); (void)hipHostFree(e->xmsg_host);
@@ -398,6 +399,7 @@ int vpic_hip_set_maxwellian_reflux(vpic_hip_engine_t *e, int code, const float *
   ENGINE(e);
   if (code > -3) VH_FAIL("custom particle boundary codes are <= -3 (got %d)", code);
   if (!ut_para || !ut_perp || n_species < 1 || n_species > MAX_SPECIES) VH_FAIL("Bad reflux parameters");
+  for (auto &w : e->walls) if (w.code == code) VH_FAIL("particle boundary code %d is a wall (vpic_hip_set_wall): it cannot be a reflux handler too", code);
   Engine::Reflux r;
   memset(&r, 0, sizeof(r));
   r.code = code;
@@ -417,6 +419,78 @@ int vpic_hip_set_reflux_draws(vpic_hip_engine_t *e, const float *draws, int64_t 
   VH_CHECK(hipMalloc(&e->reflux_draws, sizeof(float) * 3 * (size_t)n_particles));
   e->reflux_draws_n = n_particles;
   return copy_in(e, e->reflux_draws, draws, sizeof(float) * 3 * (size_t)n_particles);
+}
+// ---- absorbing walls that tally and record (the kernel side: boundary_classify_kernel, particles.hip) ----
+int vpic_hip_wall_setup(vpic_hip_engine_t *e, double quantum_q, double quantum_qke, int64_t record_cap) {
+  ENGINE(e);
+  if (!(quantum_q > 0) || !(quantum_qke > 0) || !std::isfinite(quantum_q) || !std::isfinite(quantum_qke)) VH_FAIL("wall quanta must be positive and finite");
+  if (record_cap < 0 || record_cap > (1ll << 31)) VH_FAIL("Bad wall record capacity");
+  VH_CHECK(hipStreamSynchronize(e->stream));                   // (a round that still writes into the old buffers)
+  constexpr size_t table_bytes = sizeof(vpic_hip_wall_tally_t) * VPIC_HIP_WALL_ROWS * MAX_SPECIES;
+  if (!e->wall_table) VH_CHECK(hipMalloc(&e->wall_table, table_bytes));
+  if (!e->wall_cursor) VH_CHECK(hipMalloc(&e->wall_cursor, sizeof(unsigned long long)));
+  if (record_cap != e->wall_rec_cap) {
+    if (e->wall_rec) { (void)hipFree(e->wall_rec); e->wall_rec = nullptr; }
+    e->wall_rec_cap = 0;
+    if (record_cap) VH_CHECK(hipMalloc(&e->wall_rec, sizeof(vpic_hip_wall_record_t) * (size_t)record_cap));
+    e->wall_rec_cap = record_cap;
+  }
+  VH_CHECK(hipMemsetAsync(e->wall_table, 0, table_bytes, e->stream));
+  VH_CHECK(hipMemsetAsync(e->wall_cursor, 0, sizeof(unsigned long long), e->stream));
+  if (record_cap) VH_CHECK(hipMemsetAsync(e->wall_rec, 0, sizeof(vpic_hip_wall_record_t) * (size_t)record_cap, e->stream));
+  VH_CHECK(hipStreamSynchronize(e->stream));
+  e->wall_quantum[0] = quantum_q; e->wall_quantum[1] = quantum_qke;
+  e->wall_ready = true;
+  return 0;
+}
+int vpic_hip_set_wall(vpic_hip_engine_t *e, int code, int flags) {
+  ENGINE(e);
+  if (!e->wall_ready) VH_FAIL("vpic_hip_set_wall before vpic_hip_wall_setup");
+  if (code != VPIC_ABSORB_PARTICLES && code > -3) VH_FAIL("a wall is VPIC_ABSORB_PARTICLES or a custom particle boundary code <= -3 (got %d)", code);
+  if (flags & ~(VPIC_HIP_WALL_TALLY | VPIC_HIP_WALL_RECORD)) VH_FAIL("Bad wall flags %d", flags);
+  for (auto &r : e->reflux) if (r.code == code) VH_FAIL("particle boundary code %d is a reflux handler: it cannot be a wall too", code);
+  if (flags & VPIC_HIP_WALL_RECORD) flags |= VPIC_HIP_WALL_TALLY;
+  for (size_t k = 0; k < e->walls.size(); k++)
+    if (e->walls[k].code == code) {
+      if (flags) e->walls[k].flags = flags; else e->walls.erase(e->walls.begin() + (long)k);
+      return 0;
+    }
+  if (!flags) return 0;
+  if (e->walls.size() >= VPIC_HIP_WALL_MAX) VH_FAIL("more than %d walls", (int)VPIC_HIP_WALL_MAX);
+  e->walls.push_back({code, flags});
+  return 0;
+}
+int vpic_hip_wall_tally(vpic_hip_engine_t *e, vpic_hip_wall_tally_t *out, int n_species, int clear) {
+  ENGINE(e);
+  if (!e->wall_ready) VH_FAIL("vpic_hip_wall_tally before vpic_hip_wall_setup");
+  if (!out) VH_FAIL("Bad wall tally buffer");
+  if (n_species < (int)e->species.size() || n_species < 1) VH_FAIL("wall tally: room for %d species, the engine has %d", n_species, (int)e->species.size());
+  std::vector<vpic_hip_wall_tally_t> table((size_t)VPIC_HIP_WALL_ROWS * MAX_SPECIES);
+  if (copy_out(e, table.data(), e->wall_table, sizeof(vpic_hip_wall_tally_t) * table.size())) return 1;
+  if (clear) {
+    VH_CHECK(hipMemsetAsync(e->wall_table, 0, sizeof(vpic_hip_wall_tally_t) * table.size(), e->stream));
+    VH_CHECK(hipStreamSynchronize(e->stream));
+  }
+  for (int row = 0; row < VPIC_HIP_WALL_ROWS; row++)
+    for (int sp = 0; sp < n_species; sp++)
+      out[(size_t)row * n_species + sp] = sp < MAX_SPECIES ? table[(size_t)row * MAX_SPECIES + sp] : vpic_hip_wall_tally_t{};
+  return 0;
+}
+int vpic_hip_wall_records(vpic_hip_engine_t *e, vpic_hip_wall_record_t *out, int64_t cap, int64_t *n, int64_t *dropped, int clear) {
+  ENGINE(e);
+  if (!e->wall_ready) VH_FAIL("vpic_hip_wall_records before vpic_hip_wall_setup");
+  if (cap < 0 || (cap > 0 && !out) || !n || !dropped) VH_FAIL("Bad wall record buffer");
+  unsigned long long wanted = 0;
+  if (copy_out(e, &wanted, e->wall_cursor, sizeof(wanted))) return 1;
+  const int64_t have = (int64_t)std::min<unsigned long long>(wanted, (unsigned long long)e->wall_rec_cap);
+  const int64_t m = std::min(have, cap);
+  if (m > 0 && copy_out(e, out, e->wall_rec, sizeof(vpic_hip_wall_record_t) * (size_t)m)) return 1;
+  *n = m; *dropped = (int64_t)wanted - have;
+  if (clear) {
+    VH_CHECK(hipMemsetAsync(e->wall_cursor, 0, sizeof(unsigned long long), e->stream));
+    VH_CHECK(hipStreamSynchronize(e->stream));
+  }
+  return 0;
 }
 int vpic_hip_set_emit_draws(vpic_hip_engine_t *e, const double *draws, int64_t n_slots) {
   ENGINE(e);

@@ -11,6 +11,7 @@
 // within a voxel is not the stable order of sort_p.c:67; the partition is identical).
 #include "push_device.h"
 #include "unit_draw.h"
+#include "dist_coords.h"
 #include <cstddef>
 #include <cstring>
 #include <algorithm>
@@ -792,8 +793,89 @@ struct SendTable { vpic_particle_injector_t *buf[6]; int cap; vpic_particle_inje
 struct RetryMover { vpic_particle_mover_t m; int sp, pad[3]; };                     // a mover whose message was full (resident exchange)
 // the reflux handlers as one species sees them (maxwellian_reflux.c:60-62)
 struct RefluxK { int n; int code[4]; float ut_para[4], ut_perp[4]; unsigned seed, call; const float *draws; int draws_n; };   // draws: test mode, see vpic_hip_set_reflux_draws
+// the absorbing walls that tally and record, as one species sees them (include/vpic_hip.h: vpic_hip_wall_*).  n == 0: no
+// wall is registered and the kernel does what it does without them.  row: this species' column of the table, rows of
+// row_stride; cursor[0]: records wanted since the last clear (those at or beyond rec_cap were dropped)
+struct WallK {
+  int n; int code[VPIC_HIP_WALL_MAX], flags[VPIC_HIP_WALL_MAX];
+  double quantum[2];
+  vpic_hip_wall_tally_t *row; int row_stride;
+  vpic_hip_wall_record_t *rec; long long rec_cap; unsigned long long *cursor;
+  const int64_t *tag, *tag2;
+};
 
 // three uniforms in (0,1) from a counter: seed, call, species, mover (mix32 and unit_open of unit_draw.h)
+
+// the flags of the wall registered for `code`, 0 when there is none
+__device__ __forceinline__ int wall_flags_of(const WallK &wk, int code) {
+  int flags = 0;
+  for (int k = 0; k < wk.n; k++) if (wk.code[k] == code) flags = wk.flags[k];
+  return flags;
+}
+
+// What the walls take of the movers a wavefront absorbs (all lanes that are still in the kernel call this; on: this lane's
+// mover was absorbed, at `face` (6: none), whose wall has `flags`, 0 when the face is no wall).  The lanes of one row add
+// their counts and quantised sums up across the wavefront and one of them adds to the table -- as the send-slot reservation
+// does -- and the record slots of a wavefront come from one returning atomic.
+__device__ __forceinline__ void wall_take(const WallK &wk, bool on, int face, int flags, int sp_id, int idx, int pi,
+                                          float dx, float dy, float dz, float ux, float uy, float uz, float q) {
+  const int lane = threadIdx.x & 63;
+  const int row = flags ? face : 6;
+  // the two values, quantised by the rule of vpic_hip_species_distribution_sums (distribution.hip)
+  const DistRaw raw{pi, dx, dy, dz, ux, uy, uz};
+  int cx, cy, cz;
+  const double ke = dist_coords<false>(raw, DistField{}, 1u << VPIC_HIP_COORD_KE, TileK{}, cx, cy, cz).ke;
+  const double val[2] = {(double)q, (double)q * ke};
+  long long addend[2]; bool taken[2];
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const double tq = val[k] / wk.quantum[k];
+    taken[k] = on && fabs(tq) < 4294967296.0;                                // (a NaN is refused)
+    addend[k] = taken[k] ? llrint(tq) : 0;
+  }
+  const unsigned long long here = __ballot(true);
+  unsigned long long todo = __ballot(on);
+  while (todo) {                                                            // (uniform: one turn per row present, 7 at the most)
+    const int lead = __ffsll((long long)todo) - 1;
+    const int r0 = __builtin_amdgcn_readlane(row, lead);
+    const bool shared = on && row == r0;
+    const unsigned long long same = __ballot(shared);
+    // The lanes in the kernel are lanes 0 .. n - 1 of the wavefront (the others returned at t >= nm).  Adding up from the
+    // nearest partner outwards, lane 0 ends with the sum of them all: when it reads lane m, that lane holds [m, 2m), and
+    // if it has left, so have all of those.  What a lane that has left would hand over is not looked at.
+    long long s0 = shared ? addend[0] : 0, s1 = shared ? addend[1] : 0;
+#pragma unroll
+    for (int m = 1; m <= 32; m <<= 1) {
+      const long long o0 = __shfl_xor(s0, m), o1 = __shfl_xor(s1, m);
+      if (here >> (lane ^ m) & 1ull) { s0 += o0; s1 += o1; }
+    }
+    const int ref0 = __popcll(__ballot(shared && !taken[0])), ref1 = __popcll(__ballot(shared && !taken[1]));
+    if (lane == 0) {
+      unsigned long long *w = reinterpret_cast<unsigned long long *>(wk.row + (size_t)r0 * wk.row_stride);
+      atomicAdd(w, (unsigned long long)__popcll(same));
+      if (s0) atomicAdd(w + 1, (unsigned long long)s0);                      // (two's complement: the unsigned add is the signed one)
+      if (s1) atomicAdd(w + 2, (unsigned long long)s1);
+      if (ref0) atomicAdd(w + 3, (unsigned long long)ref0);
+      if (ref1) atomicAdd(w + 4, (unsigned long long)ref1);
+    }
+    todo &= ~same;
+  }
+  const bool wants = on && (flags & VPIC_HIP_WALL_RECORD);
+  const unsigned long long m = __ballot(wants);
+  if (!m) return;
+  const int lead = __ffsll((long long)m) - 1;
+  unsigned long long base = 0;
+  if (lane == lead) base = atomicAdd(wk.cursor, (unsigned long long)__popcll(m));
+  base = __shfl(base, lead);
+  const unsigned long long slot = base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+  if (wants && slot < (unsigned long long)wk.rec_cap) {                       // (a record that does not fit is dropped: the host sees cursor > rec_cap)
+    vpic_hip_wall_record_t r;
+    r.dx = dx; r.dy = dy; r.dz = dz; r.i = pi; r.ux = ux; r.uy = uy; r.uz = uz; r.q = q;
+    r.tag = wk.tag ? wk.tag[idx] : 0; r.tag2 = wk.tag ? wk.tag2[idx] : 0;
+    r.face = face; r.sp = sp_id;
+    wk.rec[slot] = r;
+  }
+}
 
 // boundary_p.c:9-71 with atomics (several absorbed particles may share a node)
 __device__ __forceinline__ void accumulate_rhob_dev(float *rhob, float dx, float dy, float dz, float q, int pi,
@@ -844,13 +926,16 @@ int k_accumulate_rhob(Engine *e, const vpic_particle_t *host, int64_t n, float q
 // into rhob, or turned into an injector for the neighbour across the face it sits on.
 // counts: null = nm / np are the host's values; else the device-resident {movers, particles} of this species
 // (the exchange that never reads them back, vpic_hip_exchange_*): nm = min(counts[0], nm), np = counts[1].
+// WALLS: some absorbing wall that tallies or records is registered (wk.n != 0).  The instance without them never looks at
+// wk: it is the kernel as it was before there were walls.
+template <bool WALLS>
 __global__ __launch_bounds__(256)
 void boundary_classify_kernel(ParticlesK p, const vpic_particle_mover_t *__restrict__ pm, int nm, int np,
                               int sp_id, GridK g, float rdx, float rdy, float rdz, float *__restrict__ rhob,
                               SendTable send, int *__restrict__ counters, int *__restrict__ tail_flag,
                               int *__restrict__ holes, RefluxK rk, float gdx, float gdy, float gdz,
                               const int *__restrict__ nm_dev = nullptr, const int *__restrict__ np_dev = nullptr,
-                              RetryMover *__restrict__ retry = nullptr) {
+                              RetryMover *__restrict__ retry = nullptr, const WallK wk = WallK{}) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (nm_dev) {
     const int have = *nm_dev;
@@ -866,12 +951,17 @@ void boundary_classify_kernel(ParticlesK p, const vpic_particle_mover_t *__restr
   const float ux = p.ux[idx], uy = p.uy[idx], uz = p.uz[idx], q = p.q[idx];
   const int pi = record_cell(rec);
   bool absorb = true;                          // boundary_p.c:312-316: unknown interactions absorb
+  int abs_face = 6, abs_flags = 0;             // (walls only) the face that absorbed the mover, 6: none; its wall's flags
   for (int face = 0; face < 6; face++) {
     const int axis = face % 3, hi = face >= 3;
     const float d = axis == 0 ? dx : axis == 1 ? dy : dz, u = axis == 0 ? ux : axis == 1 ? uy : uz;
     const bool cond = hi ? ((d == 1.f) & (u > 0)) : ((d == -1.f) & (u < 0));     // boundary_p.c:304-309
     if (!cond) continue;
     const int code = pbc_of(g, face);
+    if (WALLS && code <= VPIC_ABSORB_PARTICLES) {                // a wall, or a plain absorbing face, absorbs here
+      abs_flags = wall_flags_of(wk, code);
+      if (abs_flags || code == VPIC_ABSORB_PARTICLES) { abs_face = face; break; }
+    }
     if (code == VPIC_ABSORB_PARTICLES) break;
     if (code < VPIC_ABSORB_PARTICLES) {
       // maxwellian_reflux.c:116-175: new momentum from the flux of a Maxwellian at the wall; what is left
@@ -951,6 +1041,7 @@ void boundary_classify_kernel(ParticlesK p, const vpic_particle_mover_t *__restr
     }
   }
   if (absorb) accumulate_rhob_dev(rhob, dx, dy, dz, q, pi, g, rdx, rdy, rdz);
+  if (WALLS) wall_take(wk, absorb, abs_face, abs_flags, sp_id, idx, pi, dx, dy, dz, ux, uy, uz, q);   // (before the slot is marked dead)
   if (nm_dev) {
     // device-resident exchange: the slot is marked dead and stays where it is (Species::n_holes, engine.h) -- nothing
     // moves under a push that is still to come, and the tile order keeps its ranges
@@ -1016,6 +1107,20 @@ __global__ void boundary_backfill_kernel(ParticlesK p, int64_t *tag, int64_t *ta
   if (tag) { tag[d] = tag[s]; tag2[d] = tag2[s]; }
 }
 
+// the walls as species k sees them (n == 0 when none is registered: the kernel then never looks at the rest)
+static WallK wall_k(const Engine *e, size_t k) {
+  WallK wk = {};
+  if (!e->wall_ready) return wk;
+  wk.n = (int)e->walls.size();
+  for (int h = 0; h < wk.n; h++) { wk.code[h] = e->walls[h].code; wk.flags[h] = e->walls[h].flags; }
+  wk.quantum[0] = e->wall_quantum[0]; wk.quantum[1] = e->wall_quantum[1];
+  wk.row = e->wall_table + k; wk.row_stride = MAX_SPECIES;
+  wk.rec = e->wall_rec; wk.rec_cap = e->wall_rec_cap; wk.cursor = e->wall_cursor;
+  const Species &s = e->species[k];
+  wk.tag = s.has_tags ? s.tag : nullptr; wk.tag2 = s.has_tags ? s.tag2 : nullptr;
+  return wk;
+}
+
 static int ensure_lists(Engine *e, int64_t n) {
   if (n <= e->list_cap) return 0;
   if (e->hole_list) { (void)hipFree(e->hole_list); (void)hipFree(e->fill_list); (void)hipFree(e->tail_flag); }
@@ -1072,9 +1177,15 @@ int k_boundary_p_pack(Engine *e) {
     rk.n = (int)e->reflux.size(); rk.seed = e->reflux_seed; rk.call = e->reflux_calls;
     rk.draws = e->reflux_draws; rk.draws_n = (int)e->reflux_draws_n;
     for (int h = 0; h < rk.n; h++) { rk.code[h] = e->reflux[h].code; rk.ut_para[h] = e->reflux[h].ut_para[k]; rk.ut_perp[h] = e->reflux[h].ut_perp[k]; }
-    hipLaunchKernelGGL(boundary_classify_kernel, dim3(nb), dim3(256), 0, e->stream, s.p, s.pm, nm, np, (int)k,
-                       e->gk, G.rdx, G.rdy, G.rdz, e->f.c[F_RHOB], send, e->counters, e->tail_flag, e->hole_list,
-                       rk, G.dx, G.dy, G.dz);
+    const WallK wk = wall_k(e, k);
+    if (wk.n)
+      hipLaunchKernelGGL(boundary_classify_kernel<true>, dim3(nb), dim3(256), 0, e->stream, s.p, s.pm, nm, np, (int)k,
+                         e->gk, G.rdx, G.rdy, G.rdz, e->f.c[F_RHOB], send, e->counters, e->tail_flag, e->hole_list,
+                         rk, G.dx, G.dy, G.dz, (const int *)nullptr, (const int *)nullptr, (RetryMover *)nullptr, wk);
+    else
+      hipLaunchKernelGGL(boundary_classify_kernel<false>, dim3(nb), dim3(256), 0, e->stream, s.p, s.pm, nm, np, (int)k,
+                         e->gk, G.rdx, G.rdy, G.rdz, e->f.c[F_RHOB], send, e->counters, e->tail_flag, e->hole_list,
+                         rk, G.dx, G.dy, G.dz, (const int *)nullptr, (const int *)nullptr, (RetryMover *)nullptr, wk);
     hipLaunchKernelGGL(boundary_fills_kernel, dim3(nb), dim3(256), 0, e->stream, e->tail_flag, nm, np - nm,
                        e->counters, e->fill_list);
     hipLaunchKernelGGL(boundary_backfill_kernel, dim3(nb), dim3(256), 0, e->stream, s.p,
@@ -1282,7 +1393,7 @@ int k_exchange_begin(Engine *e) {
 }
 
 int k_exchange_pack(Engine *e, void *const msg[6], const int32_t cap[6], int mover_cap, uint32_t species_mask) {
-  if (!e->reflux.empty()) VH_FAIL("the device-resident exchange does not serve custom particle boundary handlers");
+  if (!e->reflux.empty()) VH_FAIL("the device-resident exchange does not serve custom particle boundary handlers of the maxwellian_reflux kind");   // (they create local injectors; walls only absorb and are served)
   if (!e->retry_buf || !e->sp_table_dev) VH_FAIL("vpic_hip_exchange_pack before vpic_hip_exchange_begin");
   if (mover_cap < 1) VH_FAIL("Bad mover capacity");
   {                                                         // no launch is wider than the largest mover list
@@ -1321,9 +1432,15 @@ int k_exchange_pack(Engine *e, void *const msg[6], const int32_t cap[6], int mov
     Species &s = e->species[k];
     const int launch = (int)std::min<int64_t>(mover_cap, s.max_nm), nb = (launch + 255) / 256;
     int *nm_dev = e->counters + C_NMS + k, *np_dev = e->counters + C_NP + k;
-    hipLaunchKernelGGL(boundary_classify_kernel, dim3(nb), dim3(256), 0, e->stream, s.p, s.pm, launch, 0, (int)k,
-                       e->gk, G.rdx, G.rdy, G.rdz, e->f.c[F_RHOB], send, e->counters, (int *)nullptr, (int *)nullptr,
-                       rk, G.dx, G.dy, G.dz, nm_dev, np_dev, reinterpret_cast<RetryMover *>(e->retry_buf));
+    const WallK wk = wall_k(e, k);
+    if (wk.n)
+      hipLaunchKernelGGL(boundary_classify_kernel<true>, dim3(nb), dim3(256), 0, e->stream, s.p, s.pm, launch, 0, (int)k,
+                         e->gk, G.rdx, G.rdy, G.rdz, e->f.c[F_RHOB], send, e->counters, (int *)nullptr, (int *)nullptr,
+                         rk, G.dx, G.dy, G.dz, nm_dev, np_dev, reinterpret_cast<RetryMover *>(e->retry_buf), wk);
+    else
+      hipLaunchKernelGGL(boundary_classify_kernel<false>, dim3(nb), dim3(256), 0, e->stream, s.p, s.pm, launch, 0, (int)k,
+                         e->gk, G.rdx, G.rdy, G.rdz, e->f.c[F_RHOB], send, e->counters, (int *)nullptr, (int *)nullptr,
+                         rk, G.dx, G.dy, G.dz, nm_dev, np_dev, reinterpret_cast<RetryMover *>(e->retry_buf), wk);
     hipLaunchKernelGGL(exchange_removed_kernel, dim3(1), dim3(256), 0, e->stream, nm_dev, s.pm, launch);
     VH_CHECK(hipGetLastError());
     s.partition_valid = false;

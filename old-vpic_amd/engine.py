@@ -129,6 +129,8 @@ class CollisionDesc(C.Structure):
 
 assert C.sizeof(CollisionDesc) == 40
 SELECT_TAG_RANGE, SELECT_TAG_EVERY = 1, 2                                                      # VPIC_HIP_SELECT_*
+WallTally = collections.namedtuple("WallTally", "count isum_q isum_qke sum_q sum_qke refused")
+WallRecords = collections.namedtuple("WallRecords", "records dropped")
 SelectResult = collections.namedtuple("SelectResult", "count particles fields index")
 
 
@@ -222,6 +224,8 @@ class Engine:
             raise VpicHipError(self._l.vpic_hip_last_error().decode())
         self._h = h
         self.nv = grid.nv
+        self._n_sp = 0                                                # species created through new_species
+        self._wall_quanta, self._wall_record_cap = None, 0           # what wall_setup was given
 
     def close(self):
         if getattr(self, "_h", None):
@@ -285,6 +289,7 @@ class Engine:
         sp = self._l.vpic_hip_species_create(self._h, q_m, int(max_np), int(max_nm))
         if sp < 0:
             raise VpicHipError(self._l.vpic_hip_last_error().decode())
+        self._n_sp = max(self._n_sp, sp + 1)
         return sp
 
     def set_particles(self, sp, p):
@@ -309,6 +314,40 @@ class Engine:
     def set_maxwellian_reflux(self, code, ut_para, ut_perp, seed=1):
         a, b = np.ascontiguousarray(ut_para, np.float32), np.ascontiguousarray(ut_perp, np.float32)
         self._ck(self._l.vpic_hip_set_maxwellian_reflux(self._h, int(code), a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), len(a), int(seed)))
+
+    # ---- absorbing walls that tally and record what they take (include/vpic_hip.h: vpic_hip_wall_*) ----
+    def wall_setup(self, q_quantum, qke_quantum, record_cap=0):
+        """(Re)allocates and zeroes the tally table and the record buffer; the quanta of the sums of q and of q * ke."""
+        self._ck(self._l.vpic_hip_wall_setup(self._h, float(q_quantum), float(qke_quantum), int(record_cap)))
+        self._wall_quanta, self._wall_record_cap = (float(q_quantum), float(qke_quantum)), int(record_cap)
+
+    def set_wall(self, code, record=False, tally=True):
+        """Makes the particle boundary code a wall: ABSORB_PARTICLES itself or a code <= -3.  tally=False and
+        record=False unregister it."""
+        flags = (L.WALL_TALLY if tally or record else 0) | (L.WALL_RECORD if record else 0)
+        self._ck(self._l.vpic_hip_set_wall(self._h, int(code), flags))
+
+    def wall_tally(self, clear=False):
+        """WallTally(count, isum_q, isum_qke: int64[7, n_sp]; sum_q, sum_qke: isum * quantum, float64; refused:
+        int64[7, n_sp, 2]).  Rows 0..5: the faces -x -y -z +x +y +z where they are walls; row 6: everything else absorbed."""
+        n_sp = self._n_sp
+        if self._wall_quanta is None:                                # (the sums below need the quanta)
+            raise VpicHipError("wall_tally before this Engine's wall_setup")
+        t = np.zeros((L.WALL_ROWS, max(n_sp, 1)), L.wall_tally_t)
+        self._ck(self._l.vpic_hip_wall_tally(self._h, _ptr(t), max(n_sp, 1), int(bool(clear))))
+        t = t[:, :n_sp]
+        iq, iqke = t["isum"][..., 0].copy(), t["isum"][..., 1].copy()
+        return WallTally(t["count"].copy(), iq, iqke, iq * self._wall_quanta[0], iqke * self._wall_quanta[1], t["refused"].copy())
+
+    def wall_records(self, clear=True, cap=None):
+        """WallRecords(records: layout.wall_record_t in buffer order, dropped: records that did not fit into the device
+        buffer since it was last cleared).  cap: read at most so many (default: the buffer's capacity)."""
+        n, dropped = C.c_int64(0), C.c_int64(0)
+        if cap is None:
+            cap = self._wall_record_cap
+        out = np.zeros(int(cap), L.wall_record_t)
+        self._ck(self._l.vpic_hip_wall_records(self._h, _ptr(out) if cap else None, int(cap), C.byref(n), C.byref(dropped), int(bool(clear))))
+        return WallRecords(out[:n.value], int(dropped.value))
 
     def set_reflux_draws(self, draws):
         """Test mode: draws[k] = (uniform, normal, normal) for the particle at index k of its species' array."""

@@ -205,6 +205,8 @@ vpic_simulation::vpic_simulation() {       // src/vpic/vpic.cxx:13-49
   for (int f = 0; f < 6; f++) face_rank[f] = -1;
   comm = NULL; hip_transport = XPORT_NONE; hip_resident_exchange = false; hip_deterministic = false; x_mover_cap = 0; x_flags = 0; x_messages = x_syncs = x_recoveries = 0;
   engine = NULL; mirrors_current = false; movers_pending = false;
+  walls_on = false; plain_faces_tallied = false; wall_quantum[0] = wall_quantum[1] = 1; wall_record_cap = 0;
+  for (int f = 0; f < 6; f++) wall_pbc[f] = 0;
   for (int a = 0; a < 3; a++) { topo_index[a] = 0; topo_size[a] = 1; }
   px = py = pz = 1;
   vpic_host_current = this;
@@ -1206,9 +1208,13 @@ void vpic_simulation::create_engine(void) {
     const int id = vpic_hip_species_create(engine, sp->q_m, sp->max_np, sp->max_nm);
     if (id != (int)k) ERROR(("%s", vpic_hip_last_error()));
   }
-  for (size_t k = 0; k < reflux_handlers.size(); k++)
-    CK(vpic_hip_set_maxwellian_reflux(engine, -(int)k - 3, reflux_handlers[k].ut_para, reflux_handlers[k].ut_perp,
-                                      MAX_REFLUX_SPECIES, 0x9e3779b9u * (unsigned)(g_mp_rank + 1)));
+  for (int k = 0; k < grid->nb; k++) {
+    if (boundary_kind(k) != 0) continue;
+    const maxwellian_reflux_t *r = (const maxwellian_reflux_t *)grid->boundary[k].params;
+    CK(vpic_hip_set_maxwellian_reflux(engine, -k - 3, r->ut_para, r->ut_perp, MAX_REFLUX_SPECIES, 0x9e3779b9u * (unsigned)(g_mp_rank + 1)));
+  }
+  for (int f = 0; f < 6; f++) wall_pbc[f] = d.pbc[f];
+  start_walls();
   // the transport of the exchanges with other domains (see "exchanges with the neighbouring domains")
   hip_transport = multi() ? chosen_transport() : XPORT_NONE;
   if (hip_transport == XPORT_RCCL) {
@@ -1219,10 +1225,11 @@ void vpic_simulation::create_engine(void) {
     if (vpic_hip_comm_create(&comm, engine, id, g_mp_nproc, g_mp_rank))
       ERROR(("%s\n\t(VPIC_HIP_HOST_TRANSPORT=mpi stages the messages through host memory instead)", vpic_hip_last_error()));
   }
-  // which particle exchange: the device-resident one overlapped with the push, unless the deck has custom particle boundary
-  // handlers (the engine's resident exchange does not serve them) or asks for the reference's protocol
+  // which particle exchange: the device-resident one overlapped with the push, unless the deck has maxwellian_reflux
+  // handlers (the engine's resident exchange does not serve them: they create local injectors; walls that only absorb it
+  // does serve) or asks for the reference's protocol
   const char *xv = getenv("VPIC_HIP_HOST_EXCHANGE");
-  hip_resident_exchange = multi() && reflux_handlers.empty() && !(xv && !strcmp(xv, "legacy"));
+  hip_resident_exchange = multi() && n_boundaries(0) == 0 && !(xv && !strcmp(xv, "legacy"));
   CK(vpic_hip_set_sort_order(engine, 1));                  // the order of a sorted species is the engine's business (nothing here reads partition[]); the phased push needs it
   if (multi() && g_mp_rank == 0 && verbose)
     fprintf(stderr, "hip host: %d rank(s)%s, transport: %s, particle exchange: %s\n", g_mp_nproc, self_sends() ? " sending to itself across its periodic axes" : "",
@@ -1281,8 +1288,11 @@ void vpic_simulation::finalize(void) {
   }
   if (!getenv("VPIC_HIP_HOST_TIMING") || vpic_host_mp_rank() != 0 || !g_n_step) return;
   if (engine) vpic_hip_sync(engine);
-  fprintf(stderr, "hip host timing: %ld steps, time step %.3f ms/step, mirror refresh %.3f s, user_diagnostics %.3f s\n",
-          g_n_step, 1e3 * g_t_step / g_n_step, g_t_mirror, g_t_diag);
+  long long refused = 0;                                  // (particles an absorbing wall counted whose q or q * ke it could not add: vpic_hip_host.hxx)
+  for (size_t j = 0; j + 5 <= wall_totals.size(); j += 5) refused += wall_totals[j + 3] + wall_totals[j + 4];
+  fprintf(stderr, "hip host timing: %ld steps, time step %.3f ms/step, mirror refresh %.3f s, user_diagnostics %.3f s%s",
+          g_n_step, 1e3 * g_t_step / g_n_step, g_t_mirror, g_t_diag, walls_on ? "" : "\n");
+  if (walls_on) fprintf(stderr, ", wall sums refused %lld\n", refused);
 }
 int vpic_simulation::advance(void) {
   if (num_step > 0 && step >= num_step) return 0;
@@ -1322,6 +1332,7 @@ int vpic_simulation::advance(void) {
     mp_allsum_d(&pend, 1);
     if (pend > 0) x_exchange_rounds(num_comm_round);
   } else resident_boundary_p();                                                   // :94-96
+  refresh_walls();                                                                // (what absorb_tally and link_boundary did inside boundary_p)
   CK(vpic_hip_clear_jf_unload_accumulator(engine));                               // :109-110 in one pass over the mesh
   x_synchronize_jf();                                                             // :112
   mirrors_stale();
@@ -1735,8 +1746,11 @@ void vpic_simulation::dump_restart(const char *fbase, int fname_tag) {
     fwrite(sp->p, sizeof(particle_t), (size_t)sp->np, f);
   }
   fwrite(user_global, 1, sizeof(user_global), f);
-  put<int>(f, (int)reflux_handlers.size());
-  if (!reflux_handlers.empty()) fwrite(&reflux_handlers[0], sizeof(maxwellian_reflux_t), reflux_handlers.size(), f);
+  put<int>(f, grid->nb);                                  // the custom particle boundaries: kind and parameters (nabs, n_out among them)
+  for (int k = 0; k < grid->nb; k++) { put<int>(f, boundary_kind(k)); fwrite(grid->boundary[k].params, 1, sizeof(grid->boundary[k].params), f); }
+  put<double>(f, wall_quantum[0]); put<double>(f, wall_quantum[1]);   // (the totals below are in these units)
+  put<int>(f, (int)wall_totals.size());
+  if (!wall_totals.empty()) fwrite(&wall_totals[0], sizeof(int64_t), wall_totals.size(), f);
   std::vector<emitter_t *> ems;
   for (emitter_t *em = emitter_list; em; em = em->next) ems.push_back(em);
   put<int>(f, (int)ems.size());
@@ -1810,11 +1824,22 @@ void vpic_simulation::restart(const char *fbase) {
     if (np && fread(sp->p, sizeof(particle_t), (size_t)np, f) != (size_t)np) ERROR(("restart file is truncated"));
   }
   if (fread(user_global, 1, sizeof(user_global), f) != sizeof(user_global)) ERROR(("restart file is truncated"));
-  int nreflux;
-  get(f, nreflux);
-  reflux_handlers.resize((size_t)nreflux);
-  if (nreflux && fread(&reflux_handlers[0], sizeof(maxwellian_reflux_t), (size_t)nreflux, f) != (size_t)nreflux) ERROR(("restart file is truncated"));
-  grid->nb = nreflux;
+  int nb, ntot;
+  get(f, nb);
+  if (nb < 0 || nb > 1024) ERROR(("restart file is damaged"));
+  grid->boundary = (boundary_t *)calloc((size_t)nb + 1, sizeof(boundary_t));
+  for (int k = 0; k < nb; k++) {
+    int kind;
+    get(f, kind);
+    grid->boundary[k].handler = kind == 0 ? (boundary_handler_t)maxwellian_reflux : kind == 1 ? (boundary_handler_t)absorb_tally : (boundary_handler_t)link_boundary;
+    if (fread(grid->boundary[k].params, 1, sizeof(grid->boundary[k].params), f) != sizeof(grid->boundary[k].params)) ERROR(("restart file is truncated"));
+  }
+  grid->nb = nb;
+  get(f, wall_quantum[0]); get(f, wall_quantum[1]);
+  get(f, ntot);
+  if (ntot < 0 || ntot > 5 * 7 * 1024) ERROR(("restart file is damaged"));
+  wall_totals.resize((size_t)ntot);
+  if (ntot && fread(&wall_totals[0], sizeof(int64_t), (size_t)ntot, f) != (size_t)ntot) ERROR(("restart file is truncated"));
   int nem;
   get(f, nem);
   for (int k = 0; k < nem; k++) {
@@ -1875,14 +1900,143 @@ void vpic_simulation::run_emitters(void) {                  // advance.cxx:83-84
 
 // ---- custom particle boundaries: add_boundary (src/grid/add_boundary.c:9-35) ------------------------------
 void maxwellian_reflux(void) {}
+void absorb_tally(void) {}
+void link_boundary(void) {}
 int vpic_host_add_boundary(grid_t *g, boundary_handler_t handler, const void *params, int size) {
   vpic_simulation *sim = vpic_host_current;
   if (!g || !sim || g != sim->grid || !handler || !params) ERROR(("Add boundary encountered invalid boundary!!!"));
-  if (handler != (boundary_handler_t)maxwellian_reflux || size != (int)sizeof(maxwellian_reflux_t))
-    ERROR(("only the maxwellian_reflux particle boundary handler is supported by this host"));
-  sim->reflux_handlers.push_back(*(const maxwellian_reflux_t *)params);
-  g->nb = (int)sim->reflux_handlers.size();
-  return -((int)sim->reflux_handlers.size() - 1) - 3;
+  const bool known = (handler == (boundary_handler_t)maxwellian_reflux && size == (int)sizeof(maxwellian_reflux_t)) ||
+                     (handler == (boundary_handler_t)absorb_tally && size == (int)sizeof(absorb_tally_t)) ||
+                     (handler == (boundary_handler_t)link_boundary && size == (int)sizeof(link_boundary_t));
+  if (!known) ERROR(("only the maxwellian_reflux, absorb_tally and link_boundary particle boundary handlers are supported by this host"));
+  if (sim->resident_engine()) ERROR(("add_boundary after the run has started"));
+  boundary_t *gb = (boundary_t *)calloc((size_t)g->nb + 1, sizeof(boundary_t));     // add_boundary.c:22-31
+  if (g->nb) memcpy(gb, g->boundary, (size_t)g->nb * sizeof(boundary_t));
+  free(g->boundary);
+  g->boundary = gb;
+  gb[g->nb].handler = handler;
+  memcpy(gb[g->nb].params, params, (size_t)size);
+  return -(g->nb++) - 3;
+}
+int vpic_simulation::boundary_kind(int k) const {
+  const boundary_handler_t h = grid->boundary[k].handler;
+  return h == (boundary_handler_t)maxwellian_reflux ? 0 : h == (boundary_handler_t)absorb_tally ? 1 : 2;
+}
+int vpic_simulation::n_boundaries(int kind) const {
+  int n = 0;
+  for (int k = 0; k < grid->nb; k++) if (boundary_kind(k) == kind) n++;
+  return n;
+}
+
+// ---- absorb_tally and link_boundary: absorbing walls that tally and record on the device (include/vpic_hip.h) ----------
+void vpic_simulation::start_walls(void) {
+  const int ns = (int)species_order.size();
+  walls_on = n_boundaries(1) + n_boundaries(2) > 0;
+  if (!walls_on) return;
+  // the quanta (vpic_hip_host.hxx): from the largest |q| loaded on any rank; a restarted run keeps those its totals are in
+  if (wall_totals.empty()) {
+    double qmax = 0;
+    for (int k = 0; k < ns; k++) {
+      const species_t *sp = species_order[k];
+      for (int j = 0; j < sp->np; j++) qmax = std::max(qmax, (double)fabsf(sp->p[j].q));
+    }
+    qmax = mp_allmax_d(qmax);
+    if (!(qmax > 0) || !std::isfinite(qmax)) qmax = 1;
+    wall_quantum[0] = ldexp(qmax, -30); wall_quantum[1] = ldexp(qmax, -24);
+  }
+  // a step's rounds cannot absorb more than every species' mover list holds, round after round
+  wall_record_cap = 0;
+  if (n_boundaries(2)) { for (int k = 0; k < ns; k++) wall_record_cap += species_order[k]->max_nm; wall_record_cap *= std::max(num_comm_round, 1); }
+  CK(vpic_hip_wall_setup(engine, wall_quantum[0], wall_quantum[1], wall_record_cap));
+  int n_walls = 0;
+  if (n_boundaries(1) + n_boundaries(2) > VPIC_HIP_WALL_MAX)
+    ERROR(("this deck registers %d absorb_tally and %d link_boundary particle boundary handlers; the engine serves %d such handlers at the most",
+           n_boundaries(1), n_boundaries(2), (int)VPIC_HIP_WALL_MAX));
+  for (int k = 0; k < grid->nb; k++) {
+    if (boundary_kind(k) == 0) continue;
+    CK(vpic_hip_set_wall(engine, -k - 3, boundary_kind(k) == 2 ? VPIC_HIP_WALL_RECORD : VPIC_HIP_WALL_TALLY));
+    n_walls++;
+  }
+  // the plain absorbing faces too, while there is room (with VPIC_HIP_WALL_MAX handlers they go to row 6 with face "none")
+  plain_faces_tallied = n_walls < VPIC_HIP_WALL_MAX;
+  if (plain_faces_tallied) CK(vpic_hip_set_wall(engine, absorb_particles, VPIC_HIP_WALL_TALLY));
+  else if (g_mp_rank == 0) WARNING(("%d absorb_tally / link_boundary handlers leave no room to tally the plainly absorbing faces: wall_tally() reports them under face 6", n_walls));
+  wall_totals.resize((size_t)5 * VPIC_HIP_WALL_ROWS * (size_t)ns, 0);                  // (a restart brought them along)
+  wall_records.resize((size_t)wall_record_cap);
+}
+
+static FILE *g_link_fp = NULL;                            // link.c:33: ONE file per process, whichever handler opens it
+
+void vpic_simulation::refresh_walls(void) {
+  if (!walls_on) return;
+  const int ns = (int)species_order.size();
+  if (ns == 0) return;
+  std::vector<vpic_hip_wall_tally_t> t((size_t)VPIC_HIP_WALL_ROWS * ns);
+  CK(vpic_hip_wall_tally(engine, &t[0], ns, 1));
+  for (int row = 0; row < VPIC_HIP_WALL_ROWS; row++)
+    for (int k = 0; k < ns; k++) {
+      const vpic_hip_wall_tally_t &w = t[(size_t)row * ns + k];
+      int64_t *tot = &wall_totals[5 * ((size_t)row * ns + k)];
+      tot[0] += w.count; tot[1] += w.isum[0]; tot[2] += w.isum[1]; tot[3] += w.refused[0]; tot[4] += w.refused[1];
+      if (row == 6 || w.count == 0) continue;
+      const int b = -wall_pbc[row] - 3;
+      if (b < 0 || b >= grid->nb || boundary_kind(b) != 1) continue;
+      absorb_tally_t *at = (absorb_tally_t *)grid->boundary[b].params;                 // absorb_tally.c:24-31
+      int ispec = 0;
+      while (ispec < at->nspec && species_order[k]->id != at->id[ispec]) ispec++;
+      if (ispec == at->nspec) ERROR(("Unknown species passed to boundary handler."));
+      at->nabs[ispec] += (int)w.count;
+    }
+  if (!wall_record_cap) return;
+  int64_t n = 0, dropped = 0;
+  CK(vpic_hip_wall_records(engine, &wall_records[0], wall_record_cap, &n, &dropped, 1));
+  if (dropped) ERROR(("link_boundary: %lld records did not fit into the record buffer", (long long)dropped));
+  const grid_t *g = grid;
+  for (int64_t j = 0; j < n; j++) {
+    const vpic_hip_wall_record_t &r = wall_records[(size_t)j];
+    const int b = r.face >= 0 && r.face < 6 ? -wall_pbc[r.face] - 3 : -1;
+    if (b < 0 || b >= grid->nb || boundary_kind(b) != 2 || r.sp < 0 || r.sp >= ns) ERROR(("link_boundary: a record of face %d, species %d", (int)r.face, (int)r.sp));
+    link_boundary_t *lb = (link_boundary_t *)grid->boundary[b].params;
+    if (!g_link_fp) {                                                                  // link.c:38-56
+      char fname[512];
+      snprintf(fname, sizeof(fname), "%s.%d", lb->fbase, vpic_host_mp_rank());
+      g_link_fp = fopen(fname, "r");
+      if (g_link_fp != NULL)
+        ERROR(("File %s already exists (probably from a earlier run or "
+               "recovery) ... Please move it or change link filename", fname));
+      g_link_fp = fopen(fname, "w");
+      if (g_link_fp == NULL) ERROR(("Could not open file %s", fname));
+      fprintf(g_link_fp, "%% %17.0f\n", lb->n_out);
+    }
+    int ix, iy, iz;
+    double x, y, z;
+    iz = r.i / ((g->nx + 2) * (g->ny + 2));                                            // link.c:58-65, in its types
+    iy = (r.i - iz * (g->nx + 2) * (g->ny + 2)) / (g->nx + 2);
+    ix = r.i - (g->nx + 2) * (iy + (g->ny + 2) * iz);
+    x = g->x0 + ((ix - 1) + (r.dx + 1) * 0.5) * g->dx;
+    y = g->y0 + ((iy - 1) + (r.dy + 1) * 0.5) * g->dy;
+    z = g->z0 + ((iz - 1) + (r.dz + 1) * 0.5) * g->dz;
+    fprintf(g_link_fp, "%d %e %e %e %e %e %e %e\n", species_order[r.sp]->id, x, y, z, r.ux, r.uy, r.uz, r.q);
+    lb->n_out++;
+  }
+  if (g_link_fp && n) fflush(g_link_fp);
+}
+
+void vpic_simulation::wall_tally(int face, species_t *sp, int64_t *count, double *charge, double *energy) {
+  if (count) *count = 0;
+  if (charge) *charge = 0;
+  if (energy) *energy = 0;
+  if (face < 0 || face >= VPIC_HIP_WALL_ROWS || !sp) ERROR(("Bad wall_tally arguments"));
+  if (walls_on && face < 6 && wall_pbc[face] == absorb_particles && !plain_faces_tallied)
+    ERROR(("wall_tally: face %d absorbs plainly and is not tallied by itself (%d handlers are registered); ask for face 6", face, (int)VPIC_HIP_WALL_MAX));
+  const int ns = (int)species_order.size();
+  for (int k = 0; k < ns; k++) {
+    if (species_order[k] != sp || wall_totals.size() < (size_t)5 * VPIC_HIP_WALL_ROWS * ns) continue;
+    const int64_t *tot = &wall_totals[5 * ((size_t)face * ns + k)];
+    if (count) *count = tot[0];
+    if (charge) *charge = (double)tot[1] * wall_quantum[0];
+    if (energy) *energy = (double)tot[2] * wall_quantum[1];
+  }
 }
 
 // ---- L3 entry points for deck code ------------------------------------------------------------------

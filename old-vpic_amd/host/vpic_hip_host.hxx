@@ -26,8 +26,9 @@
 // dump of the reference (energies, fields, hydro, particles, grid, species, materials, the strided
 // field_dump / hydro_dump with their .vpc header) and restart files (dump_restart, `restart <fbase>`).
 // Particles a deck injects while the run is under way (inject_particle / inject_particle_raw from
-// user_particle_injection) reach the device at the end of that call.  maxwellian_reflux boundaries (add_boundary); surface emitters with the child_langmuir / ccube / ivory laws.
-// Not there: other custom particle boundary handlers, set_region_bc.  Unsupported calls stop with the reference's ERROR convention (message, exit(1)).
+// user_particle_injection) reach the device at the end of that call.  The custom particle boundaries the reference ships
+// (add_boundary): maxwellian_reflux, absorb_tally and link_boundary; surface emitters with the child_langmuir / ccube / ivory laws.
+// Not there: particle boundary handlers of a deck's own, set_region_bc.  Unsupported calls stop with the reference's ERROR convention (message, exit(1)).
 // uniform_rand() is the reference's generator (MT19937 + its 53-bit open-interval conversion,
 // src/util/mtrand/mtrand.c:69-76,240, mtrand_conv.h:61); maxwellian_rand() uses Box-Muller on it
 // instead of the reference's 256-layer ziggurat (whose tables are a data file of the reference), so
@@ -153,10 +154,35 @@ void sort_p(species_t *sp, const grid_t *g);
 // Custom particle boundary handlers (src/boundary/boundary.h, src/grid/grid.h:170-190): a deck fills a
 // maxwellian_reflux_t, registers it with add_boundary( grid, maxwellian_reflux, &params ) and gives the code it
 // gets back (<= -3) to set_domain_particle_bc.  maxwellian_reflux here is only the handler's NAME: the work is
-// done on the device (vpic_hip_set_maxwellian_reflux).  Other handlers are refused.
+// done on the device (vpic_hip_set_maxwellian_reflux).
+// absorb_tally and link_boundary (boundary.h:35-59) are absorbing walls that tally and record on the device
+// (include/vpic_hip.h: vpic_hip_wall_*).  Codes are -(k + 3) in registration order across all kinds (add_boundary.c:31);
+// grid->boundary[k].params holds the copy of handler k's parameters, which a deck reads as in the reference:
+//   ((absorb_tally_t *)grid->boundary[-code - 3].params)->nabs[j]
+// nabs is brought up to date once per step, after the step's particle exchange: for the species in id[], the particles
+// absorbed at the faces of this domain that carry the handler's code; a species absorbed there that is not in id[] stops
+// the run with the reference's message.  link_boundary writes the reference's file, <fbase>.<rank>, created at the first
+// step that absorbs something there (a file that already exists stops the run), "%% %17.0f\n" of n_out at that moment and
+// one line "%d %e %e %e %e %e %e %e\n" per particle (species id, x, y, z, ux, uy, uz, q; link.c:53-67); n_out grows by the
+// lines written.  As in the reference the file is ONE per process: a second link handler writes into the first one's.
+// Other handlers are refused.
+// LIMIT: the engine serves 4 wall codes (VPIC_HIP_WALL_MAX).  A deck may register up to 4 absorb_tally / link_boundary
+// handlers in all (maxwellian_reflux handlers do not count; they have 4 of their own); a fifth stops the run at its start
+// with a message that says so.  With fewer than 4 the plainly absorbing faces (absorb_particles) are tallied face by face
+// as well; with exactly 4 there is no code left for them: what they absorb is counted under face 6 with the movers no
+// face took, a warning says so at the start, and wall_tally() for such a face stops the run instead of answering zero.
+// The quanta of the walls' exact sums (vpic_hip_wall_setup) are chosen when the run starts from the largest |q| loaded
+// on any rank, qmax (1 when nothing is charged): charge in units of qmax 2^-30, q * ke in units of qmax 2^-24 -- no
+// loaded charge can be refused, nor one four times heavier, nor q * ke below ke = 256; what is refused all the same is
+// reported in the closing timing line.
 typedef struct maxwellian_reflux { float ut_perp[32], ut_para[32]; } maxwellian_reflux_t;
+typedef struct absorb_tally { int nspec; species_id id[32]; int nabs[32]; } absorb_tally_t;
+typedef struct link_boundary { char fbase[256]; double n_out; } link_boundary_t;
 typedef void (*boundary_handler_t)(void);
+typedef vpic_boundary_t boundary_t;
 void maxwellian_reflux(void);
+void absorb_tally(void);
+void link_boundary(void);
 int vpic_host_add_boundary(grid_t *g, boundary_handler_t handler, const void *params, int size);
 #define add_boundary(g, bh, ip) vpic_host_add_boundary((g), (boundary_handler_t)(bh), (ip), (int)sizeof(*(ip)))
 
@@ -303,6 +329,13 @@ public:
   void resident_advance_p(int id);                  // push one resident species; its movers wait for ...
   void resident_boundary_p(void);                   // ... the exchange of every resident species with pending movers
   double resident_energy_p(const particle_t *p0);
+  // What the absorbing walls of this domain took of a species since the run began (restarts included): face 0..5 (-x -y -z
+  // +x +y +z), where that face carries an absorb_tally or link_boundary handler or -- in a deck that has such a handler --
+  // is plainly absorbing; face 6: every other particle absorbed.  count, charge (the sum of q) and energy (the sum of
+  // q * ke, ke = gamma - 1) in the deck's units, from exact integer sums (include/vpic_hip.h).  Any pointer may be NULL.
+  // Zero throughout in a deck without such handlers.  A plainly absorbing face of a deck with 4 handlers is not tallied
+  // by itself (LIMIT above): asking for it is an ERROR.
+  void wall_tally(int face, species_t *sp, int64_t *count, double *charge, double *energy);
   // The energy diagnostic of the production deck (decks/trecon-part/energy.cxx:89-162) from the resident state, in place
   // of a loop over sp->p, which would download the whole species: bands[k * nv + voxel] (nex * nv floats, or NULL) the
   // share of the voxel's particles in each of nex linear bands of width dke, ghost voxels filled from their interior
@@ -391,8 +424,16 @@ private:
   void flush_injected(void);
   void run_emitters(void);
 public:
-  std::vector<maxwellian_reflux_t> reflux_handlers;   // handler k answers to particle code -(k+3)
+  int boundary_kind(int k) const;                   // of grid->boundary[k]: 0 maxwellian_reflux, 1 absorb_tally, 2 link_boundary
+  int n_boundaries(int kind) const;
 private:
+  // absorbing walls (absorb_tally, link_boundary): the codes of this domain's faces, the quanta, the totals since the run
+  // began as [7][species] {count, isum q, isum q ke, refused q, refused q ke}, and the records' staging buffer
+  int wall_pbc[6]; bool walls_on, plain_faces_tallied; double wall_quantum[2]; int64_t wall_record_cap;
+  std::vector<int64_t> wall_totals;
+  std::vector<vpic_hip_wall_record_t> wall_records;
+  void start_walls(void);
+  void refresh_walls(void);                         // once per step: nabs, the link file
   void queue_injected(species_t *sp, const particle_t &p);
   void box(double xl, double yl, double zl, double xh, double yh, double zh, int nx, int ny, int nz, int pbc, int fbc);
   void slab(double gx0, double gy0, double gz0, double gx1, double gy1, double gz1, int gnx, int gny, int gnz,

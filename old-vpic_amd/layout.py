@@ -38,6 +38,14 @@ material_coefficient_t = np.dtype([("decayx", "f4"), ("drivex", "f4"), ("decayy"
                                    ("rmuz", "f4"), ("nonconductive", "f4"), ("epsx", "f4"), ("epsy", "f4"),
                                    ("epsz", "f4"), ("pad", "f4", (3,))], align=True)
 
+# what an absorbing wall takes (include/vpic_hip.h: vpic_hip_wall_tally_t, vpic_hip_wall_record_t)
+wall_tally_t = np.dtype([("count", "i8"), ("isum", "i8", (2,)), ("refused", "i8", (2,))], align=True)
+wall_record_t = np.dtype([("dx", "f4"), ("dy", "f4"), ("dz", "f4"), ("i", "i4"),
+                          ("ux", "f4"), ("uy", "f4"), ("uz", "f4"), ("q", "f4"),
+                          ("tag", "i8"), ("tag2", "i8"), ("face", "i4"), ("sp", "i4")], align=True)
+WALL_TALLY, WALL_RECORD, WALL_ROWS = 1, 2, 7
+assert wall_tally_t.itemsize == 40 and wall_record_t.itemsize == 56
+
 assert particle_t.itemsize == 48 and particle_mover_t.itemsize == 16 and particle_injector_t.itemsize == 48
 assert interpolator_t.itemsize == 80 and accumulator_t.itemsize == 48 and field_t.itemsize == 80
 assert material_coefficient_t.itemsize == 64
