@@ -272,6 +272,70 @@ int vpic_hip_push_plan(int64_t np, int iters, int64_t *start, int32_t *count, ui
  * (src/vpic/vpic.hxx:491-505), on the device with a counter-based generator. */
 int vpic_hip_species_load_maxwellian(vpic_hip_engine_t *e, int sp, int ppc, uint32_t seed, float q,
                                      float ux, float uy, float uz, float vth);
+/* A species loaded on the device from per-cell tables, the same particles for any decomposition of the global grid.
+ * (The synthetic loader above keys its draws with a 32-bit particle index times 9, so its streams repeat from 477 M
+ * particles of a species on; it stays as it is because the benchmark and the tests that pin its draws rest on it.)
+ *
+ * Tables are HOST arrays of tdim[0] * tdim[1] * tdim[2] entries, x fastest; every tdim entry is 1 (the table does not vary
+ * along that axis) or the grid's extent; all tables of a call share tdim and are uploaded as given.  A NULL ud / uth
+ * table reads 0.  count[] macro-particles go into each cell, each of charge q[]; ud is the cell's drift as gamma_d beta_d,
+ * uth the spread of the momentum u = gamma beta in the drift's rest frame.
+ *
+ * THE RULE (old-vpic_amd/csrc/load_rule.h; tests/load_ref.py restates it in numpy):
+ *   Generator, Philox-4x32-10: M0 = 0xD2511F53, M1 = 0xCD9E8D57, W0 = 0x9E3779B9, W1 = 0xBB67AE85.  One round on counter
+ *   (c0,c1,c2,c3) and key (k0,k1): p0 = M0 * c0, p1 = M1 * c2 as 64-bit products; the new counter is
+ *   (hi(p1) ^ c1 ^ k0, lo(p1), hi(p0) ^ c3 ^ k1, lo(p0)).  Ten rounds; before each of rounds 2 to 10, k0 += W0 and k1 += W1
+ *   in uint32 arithmetic.  (Counter 0, key 0 gives 6627e8d5 e169c58d bc57ac4c 9b00dbd8.)
+ *   Keys and counters: the key is (seed, stream).  A particle is named by its global cell c = gx + GX * (gy + GY * gz)
+ *   (global cell coordinates from 0, c 64-bit: g = goff + local cell) and its number j within the cell for this call, from
+ *   0.  Block b (0 or 1) is philox((lo32(c), hi32(c), j, b), key); the words r0..r3 (block 0) and r4..r7 (block 1) are the
+ *   particle's draws.  Rank, array order and launch shape do not enter.
+ *   From draws to numbers (unit_open: ((float)(r >> 8) + 0.5f) * 2^-24, at most 1 - 2^-24):  x_k = unit_open(r_k), k = 0, 1, 2;
+ *   n0 = R1 cos(2 pi unit_open(r4)), n1 = R1 sin(2 pi unit_open(r4)) with R1 = sqrt(-2 log unit_open(r3));
+ *   n2 = sqrt(-2 log unit_open(r5)) cos(2 pi unit_open(r6));  U = unit_open(r7).  The normals use the device's own float
+ *   log, cos and sin and are specified statistically, as the draws of vpic_hip_collide are; x_k and U are exact.  With
+ *   vpic_hip_set_load_draws (parity tests) the seven floats (x0, x1, x2, n0, n1, n2, U) are read from draws[7 m .. 7 m + 6],
+ *   m the particle's place within the call's load (below).
+ *   From numbers to the particle, every operation rounded once, uncontracted, parentheses as written:
+ *     dx = 2.f * x0 - 1.f, dy and dz likewise (strictly inside (-1, 1)); voxel i = (cx+1) + sy (cy+1) + sz (cz+1); q the
+ *     cell's table value.  Momentum in IEEE double from the float tables, / and sqrt correctly rounded:
+ *       w_k = (double)uth_k[cell] * (double)n_k;   gw = sqrt(1 + ((w0 w0 + w1 w1) + w2 w2))
+ *       D_k = (double)ud_k[cell];                   D2 = (D0 D0 + D1 D1) + D2 D2
+ *       if D2 == 0: u_k = w_k.  Otherwise:
+ *         gd = sqrt(1 + D2);  wD = (w0 D0 + w1 D1) + w2 D2
+ *         with VPIC_HIP_LOAD_FLIP, if (-wD) / (gd * gw) > (double)U:  t = (2 * wD) / D2;  w_k = w_k - t * D_k;  wD = -wD
+ *           (Zenitani's flipping method, Phys. Plasmas 22, 042116 (2015): the boosted population has the right density in
+ *           the lab frame; a no-op in the non-relativistic limit)
+ *         f = ((gd - 1) * wD) / D2 + gw;   u_k = w_k + f * D_k
+ *       ux, uy, uz = (float)u_0, (float)u_1, (float)u_2
+ *     Tags with VPIC_HIP_LOAD_TAGS: tag = tag0 + m, tag2 = 0; otherwise the new particles' tags read 0.
+ *   Order: the call's particles are ordered by ascending voxel, and by ascending j within a cell: m = offset[cell] + j,
+ *   offset the exclusive sum of the counts in that order.
+ *
+ * Without VPIC_HIP_LOAD_APPEND the call replaces the species and leaves it as a by-voxel sort_p does: the array in voxel
+ * order, partition[] written (ghost voxels as empty ranges), vpic_hip_species_sort_order 1.  With it the particles go
+ * behind the species' extent, booked as vpic_hip_species_append_particles books them (several populations in one species).
+ * q_max rises to the largest |q| of a cell with a non-zero count; the species is chargeless when every such q is 0 (and, with
+ * APPEND, it was before); has_tags follows the TAGS flag (with APPEND, a species that had tags keeps them).
+ * Refused with nothing touched (vpic_hip_last_error names the argument): a NULL d, count or q; an unknown sp; a tdim
+ * entry neither 1 nor the grid's extent; goff < 0 or goff + n > gdim; a negative count; a non-finite q, ud or uth; a
+ * negative uth; unknown flag bits; a total above 2^31 - 1 or beyond the free capacity; a draws table shorter than the
+ * total; a species with pending movers.  *n_loaded (may be NULL): the particles the call added. */
+#define VPIC_HIP_LOAD_APPEND 1
+#define VPIC_HIP_LOAD_FLIP 2
+#define VPIC_HIP_LOAD_TAGS 4
+typedef struct {
+  const int32_t *count;        /* macro-particles per cell, >= 0 */
+  const float *q;              /* charge of each macro-particle of the cell */
+  const float *ud[3], *uth[3]; /* drift gamma beta and thermal spread of u, by x y z; a NULL table reads 0 */
+  int32_t tdim[3];             /* extents of EVERY table along x, y, z: each 1 (broadcast) or the grid's n; x fastest */
+  int64_t gdim[3], goff[3];    /* the global grid and this domain's first cell in it */
+  uint32_t seed, stream; int32_t flags; int64_t tag0;
+} vpic_hip_load_t;
+VPIC_HIP_STATIC_ASSERT(sizeof(vpic_hip_load_t) == 152, "vpic_hip_load_t layout");
+int vpic_hip_species_load_profile(vpic_hip_engine_t *e, int sp, const vpic_hip_load_t *d, int64_t *n_loaded);
+/* parity mode of the call above: seven floats per particle place m replace the generator's numbers; n = 0 switches back */
+int vpic_hip_set_load_draws(vpic_hip_engine_t *e, const float *draws, int64_t n);
 int64_t vpic_hip_species_np(vpic_hip_engine_t *e, int sp);               /* live particles */
 /* extent = array slots in use (live particles + the dead slots the device-resident exchange leaves until the next sort),
  * and the capacities; _reserve enlarges them between steps (boundary_p.c:416-448 grows by 1.3125 when it runs out) */

@@ -121,6 +121,9 @@ def lib():
         L.vpic_hip_set_wall.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.vpic_hip_wall_tally.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.vpic_hip_wall_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
+    if hasattr(L, "vpic_hip_species_load_profile"):         # (an older build under VPIC_HIP_LIB has no profile loader)
+        L.vpic_hip_species_load_profile.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.vpic_hip_set_load_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     L.vpic_hip_dump_gather.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_size_t]
     _lib = L
     return L
@@ -145,4 +148,5 @@ vpic_hip_cell_distribution vpic_hip_cell_distribution_stats
 vpic_hip_species_select_count vpic_hip_species_select vpic_hip_species_select_stats
 vpic_hip_accumulate_hydro_p_select
 vpic_hip_wall_setup vpic_hip_set_wall vpic_hip_wall_tally vpic_hip_wall_records
-vpic_hip_collide vpic_hip_collide_relativistic vpic_hip_collide_stats vpic_hip_collide_instance vpic_hip_set_collide_draws""".split()
+vpic_hip_collide vpic_hip_collide_relativistic vpic_hip_collide_stats vpic_hip_collide_instance vpic_hip_set_collide_draws
+vpic_hip_species_load_profile vpic_hip_set_load_draws""".split()

@@ -420,6 +420,10 @@ struct Engine {
   float *collide_draws = nullptr; int64_t collide_draws_n = 0;
   unsigned long long *collide_dev = nullptr, *collide_host = nullptr;
   int64_t collide_last[6] = {0, 0, 0, 0, 0, 0}; int collide_instance = 0;
+  // species loaded from per-cell tables (load.hip), allocated by the first call and grown on demand: the parity mode's draws
+  // (7 floats per particle place) and the call's tables as uploaded
+  float *load_draws = nullptr; int64_t load_draws_n = 0;
+  char *load_tab = nullptr; size_t load_tab_bytes = 0;
 
   hipEvent_t step_done[4] = {}; int64_t steps_enqueued = 0;   // vpic_hip_step: the host stays at most two steps ahead of the device
   // profiling
@@ -496,6 +500,8 @@ inline bool tile_partition_usable(const Species &s, const TileK &t) {
 int k_particles_from_aos(Engine *e, Species &s, const vpic_particle_t *host, int64_t n_new, int64_t at = 0, bool any_voxel = false);   // any_voxel: ghost voxels pass too (a test hook's: such a species may be sorted, never pushed)
 int k_particles_to_aos(Engine *e, Species &s, vpic_particle_t *host, int64_t cap, int64_t from = 0, int64_t count = -1);
 int k_load_maxwellian(Engine *e, Species &s, int ppc, unsigned seed, float q, float ux, float uy, float uz, float vth);
+int ensure_tags(Engine *e, Species &s);                                          // the species' tag arrays, zeroed when first allocated
+int k_load_profile(Engine *e, Species &s, const vpic_hip_load_t &d, int64_t *n_loaded);   // load.hip: checks, uploads, scans, generates
 int k_energy_p(Engine *e, Species &s, double *energy);
 int k_center_p(Engine *e, Species &s, bool uncenter);
 int k_energy_spectrum(Engine *e, Species &s, const vpic_hip_spectrum_t &sp);   // into Engine::spec_lin / spec_log / spec_log_host; waits for the stream

@@ -195,6 +195,7 @@ static void destroy(Engine *e) {
   (void)hipFree(e->local_buf); (void)hipFree(e->reflux_draws); (void)hipFree(e->emit_draws);
   (void)hipFree(e->wall_table); (void)hipFree(e->wall_rec); (void)hipFree(e->wall_cursor);
   (void)hipFree(e->collide_draws); (void)hipFree(e->collide_dev); (void)hipHostFree(e->collide_host);
+  (void)hipFree(e->load_draws); (void)hipFree(e->load_tab);
   (void)hipFree(e->hole_list); (void)hipFree(e->fill_list); (void)hipFree(e->tail_flag);
   (void)hipFree(e->sp_table_dev); (void)hipHostFree(e->sp_table_host); (void)hipFree(e->xmsg_dev); (void)hipHostFree(e->xmsg_host);
   (void)hipFree(e->retry_buf); (void)hipFree(e->tile_list[0]); (void)hipFree(e->tile_list[1]);
@@ -528,6 +529,22 @@ int vpic_hip_species_load_maxwellian(vpic_hip_engine_t *e, int sp, int ppc, uint
                                      float ux, float uy, float uz, float vth) {
   ENGINE(e); SPECIES(e, sp);
   return k_load_maxwellian(e, e->species[sp], ppc, seed, q, ux, uy, uz, vth);
+}
+int vpic_hip_species_load_profile(vpic_hip_engine_t *e, int sp, const vpic_hip_load_t *d, int64_t *n_loaded) {
+  ENGINE(e);
+  if (sp < 0 || (size_t)sp >= e->species.size()) VH_FAIL("load_profile: sp = %d is not a species", sp);
+  if (!d) VH_FAIL("load_profile: d is NULL");
+  return k_load_profile(e, e->species[sp], *d, n_loaded);
+}
+int vpic_hip_set_load_draws(vpic_hip_engine_t *e, const float *draws, int64_t n) {
+  ENGINE(e);
+  if (n < 0 || (n > 0 && !draws) || n > (1ll << 28)) VH_FAIL("Bad draw table");
+  if (e->load_draws) { (void)hipFree(e->load_draws); e->load_draws = nullptr; }
+  e->load_draws_n = 0;
+  if (n == 0) return 0;
+  VH_CHECK(hipMalloc(&e->load_draws, sizeof(float) * 7 * (size_t)n));
+  e->load_draws_n = n;
+  return copy_in(e, e->load_draws, draws, sizeof(float) * 7 * (size_t)n);
 }
 int64_t vpic_hip_species_np(vpic_hip_engine_t *e, int sp) {
   if (!e || sp < 0 || (size_t)sp >= e->species.size()) return -1;

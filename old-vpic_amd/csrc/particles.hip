@@ -46,7 +46,7 @@ static int alloc_particles_raw_impl(ParticlesK &p, int64_t n);
 static int alloc_particles_raw(ParticlesK &p, int64_t n) { return alloc_particles_raw_impl(p, n); }
 static const int64_t CHUNK = 8 << 20;   // particles per staging round trip (384 MiB)
 
-static int ensure_tags(Engine *e, Species &s) {
+int ensure_tags(Engine *e, Species &s) {
   if (s.tag) return 0;
   VH_CHECK(hipMalloc(&s.tag, sizeof(int64_t) * s.max_np));
   VH_CHECK(hipMalloc(&s.tag2, sizeof(int64_t) * s.max_np));

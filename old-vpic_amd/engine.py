@@ -382,6 +382,52 @@ class Engine:
         """ppc synthetic particles in every interior cell (device-side loader)."""
         self._ck(self._l.vpic_hip_species_load_maxwellian(self._h, sp, int(ppc), int(seed), q, u[0], u[1], u[2], vth))
 
+    def load_profile(self, sp, count, q, ud=None, uth=None, *, seed, stream=0, global_dims=None, offset=(0, 0, 0),
+                     flip=False, tags=None, append=False):
+        """Load a species on the device from per-cell tables (include/vpic_hip.h: vpic_hip_species_load_profile, THE RULE).
+        count, q and the entries of the triples ud (drift gamma beta) and uth (thermal spread of u) are scalars or numpy
+        arrays shaped [tz, ty, tx], every extent 1 or the grid's; they are broadcast against each other to one shape.
+        global_dims / offset: the whole grid (x, y, z) and this domain's first cell in it (default: this grid is the whole
+        one).  tags=tag0 numbers the particles tag0, tag0 + 1, ... in the call's order.  Returns the particles loaded."""
+        g = self.grid
+        tabs = [np.asarray(count), np.asarray(q)]
+        for triple in (ud, uth):
+            if triple is not None and len(triple) != 3:
+                raise VpicHipError("load_profile: ud and uth are triples (x, y, z)")
+            tabs += [None if triple is None or triple[a] is None else np.asarray(triple[a]) for a in range(3)]
+        for t in tabs:
+            if t is not None and t.ndim not in (0, 3):
+                raise VpicHipError(f"load_profile: a table is a scalar or shaped [tz, ty, tx], got shape {t.shape}")
+        try:
+            shape = np.broadcast_shapes(*[(1, 1, 1) if t is None or t.ndim == 0 else t.shape for t in tabs])
+        except ValueError as err:
+            raise VpicHipError(f"load_profile: the tables do not broadcast to one shape ({err})") from None
+        keep = [None if t is None else np.ascontiguousarray(np.broadcast_to(t, shape), np.int32 if k == 0 else np.float32)
+                for k, t in enumerate(tabs)]
+        if not np.array_equal(keep[0], np.broadcast_to(tabs[0], shape)):
+            raise VpicHipError("load_profile: count holds values that are not 32-bit integers")
+        d = np.zeros(1, L.load_t)
+        addr = [0 if t is None else t.ctypes.data for t in keep]
+        d["count"], d["q"], d["ud"], d["uth"] = addr[0], addr[1], addr[2:5], addr[5:8]
+        d["tdim"] = shape[::-1]
+        d["gdim"] = (g.nx, g.ny, g.nz) if global_dims is None else tuple(int(v) for v in global_dims)
+        d["goff"] = tuple(int(v) for v in offset)
+        d["seed"], d["stream"] = int(seed) & 0xffffffff, int(stream) & 0xffffffff
+        d["flags"] = (L.LOAD_APPEND if append else 0) | (L.LOAD_FLIP if flip else 0) | (L.LOAD_TAGS if tags is not None else 0)
+        d["tag0"] = 0 if tags is None else int(tags)
+        n = C.c_int64(0)
+        self._ck(self._l.vpic_hip_species_load_profile(self._h, int(sp), _ptr(d), C.byref(n)))
+        return int(n.value)
+
+    def set_load_draws(self, draws):
+        """Test mode of load_profile(): draws[m] = (x0, x1, x2, n0, n1, n2, U) for the particle at place m of a call's load,
+        float32[n, 7]; None switches back to the device's generator."""
+        if draws is None:
+            self._ck(self._l.vpic_hip_set_load_draws(self._h, None, 0))
+            return
+        d = np.ascontiguousarray(draws, np.float32).reshape(-1, 7)
+        self._ck(self._l.vpic_hip_set_load_draws(self._h, d.ctypes.data_as(C.c_void_p), len(d)))
+
     def np(self, sp):
         return int(self._l.vpic_hip_species_np(self._h, sp))
 

@@ -570,6 +570,7 @@ void vpic_simulation::describe(vpic_hip_grid_t &d) {
 }
 
 static int64_t g_particle_downloads = 0;     // whole-species downloads into the host mirrors (vpic_simulation::particle_mirror_downloads)
+static int64_t g_particle_uploads = 0;       // particles that went from a host mirror to the device (vpic_simulation::particle_mirror_uploads)
 int vpic_simulation::resident_id(const particle_t *p0) const {
   if (!engine) return -1;
   for (size_t k = 0; k < species_order.size(); k++) if (species_order[k]->p == p0) return (int)k;
@@ -689,6 +690,45 @@ int64_t vpic_simulation::select_particles(species_t *sp, const vpic_hip_select_t
   return count;
 }
 int64_t vpic_simulation::particle_mirror_downloads(void) const { return g_particle_downloads; }
+int64_t vpic_simulation::particle_mirror_uploads(void) const { return g_particle_uploads; }
+
+// A species loaded on the device from per-cell tables (vpic_hip_species_load_profile).  Before the run has started (from
+// begin_initialization) the call is kept, tables and all, and carried out when the engine exists, behind the upload of
+// what the deck injected on the host; later it is carried out at once.
+void vpic_simulation::run_profile_load(const profile_load_t &l) {
+  int id = -1;
+  for (size_t k = 0; k < species_order.size(); k++) if (species_order[k] == l.sp) id = (int)k;
+  if (id < 0) ERROR(("load_species_profile: not a species of this simulation"));
+  vpic_hip_load_t d = l.d;
+  d.count = &l.count[0]; d.q = &l.tab[0][0];
+  for (int a = 0; a < 3; a++) {
+    d.ud[a] = l.tab[1 + a].empty() ? NULL : &l.tab[1 + a][0];
+    d.uth[a] = l.tab[4 + a].empty() ? NULL : &l.tab[4 + a][0];
+  }
+  const int n[3] = {grid->nx, grid->ny, grid->nz};
+  for (int a = 0; a < 3; a++) { d.gdim[a] = (int64_t)n[a] * topo_size[a]; d.goff[a] = (int64_t)n[a] * topo_index[a]; }
+  int64_t loaded = 0;
+  CK(vpic_hip_species_load_profile(engine, id, &d, &loaded));
+  l.sp->np = (int)vpic_hip_species_np(engine, id);        // the count stays current; the array is stale, as after a push
+}
+void vpic_simulation::load_species_profile(species_t *sp, const vpic_hip_load_t &d) {
+  if (!sp) ERROR(("Invalid species"));
+  if (!d.count || !d.q) ERROR(("load_species_profile: count and q tables are needed"));
+  size_t T = 1;
+  for (int a = 0; a < 3; a++) {
+    if (d.tdim[a] < 1) ERROR(("load_species_profile: tdim[%d] = %d", a, d.tdim[a]));
+    T *= (size_t)d.tdim[a];
+  }
+  profile_load_t l;
+  l.sp = sp; l.d = d;
+  l.count.assign(d.count, d.count + T);
+  const float *tabs[7] = {d.q, d.ud[0], d.ud[1], d.ud[2], d.uth[0], d.uth[1], d.uth[2]};
+  for (int a = 0; a < 7; a++) if (tabs[a]) l.tab[a].assign(tabs[a], tabs[a] + T);
+  if (!engine) { pending_loads.push_back(l); return; }
+  mirrors_after_user_code();                              // what the hook wrote so far goes to the device first
+  run_profile_load(l);
+  mirrors_stale();
+}
 bool vpic_simulation::resident_energy_f(double *en, const field_t *f) {
   if (!engine || f != field) return false;
   CK(vpic_hip_energy_f(engine, en));
@@ -733,7 +773,7 @@ void vpic_simulation::mirrors_after_user_code(void) {
     if (m.state != M_DIRTY) continue;
     if (m.kind == 0) { CK(vpic_hip_set_fields(engine, field)); fields_changed = true; }
     else if (m.kind == 1) CK(vpic_hip_set_interpolator(engine, interpolator));
-    else CK(vpic_hip_species_set_particles(engine, m.sp, species_order[m.sp]->p, species_order[m.sp]->np));
+    else { CK(vpic_hip_species_set_particles(engine, m.sp, species_order[m.sp]->p, species_order[m.sp]->np)); g_particle_uploads += species_order[m.sp]->np; }
   }
   (void)fields_changed;
   mirrors_stale();
@@ -788,8 +828,10 @@ void vpic_simulation::hip_sync_mirrors(void) {
 void vpic_simulation::hip_upload_mirrors(void) {
   if (g_demand) { mirrors_after_user_code(); CK(vpic_hip_load_interpolator(engine)); return; }   // what the deck wrote, nothing else
   CK(vpic_hip_set_fields(engine, field));
-  for (size_t k = 0; k < species_order.size(); k++)
+  for (size_t k = 0; k < species_order.size(); k++) {
     CK(vpic_hip_species_set_particles(engine, (int)k, species_order[k]->p, species_order[k]->np));
+    g_particle_uploads += species_order[k]->np;
+  }
   CK(vpic_hip_load_interpolator(engine));
   mirrors_stale();
 }
@@ -1226,6 +1268,8 @@ void vpic_simulation::create_engine(void) {
     fprintf(stderr, "hip host: %d rank(s)%s, transport: %s, particle exchange: %s\n", g_mp_nproc, self_sends() ? " sending to itself across its periodic axes" : "",
             transport_name(), hip_resident_exchange ? "device-resident, overlapped with the push" : "count-then-payload (boundary_p.c)");
   hip_upload_mirrors();                                   // fields, particles (and a first load_interpolator)
+  for (size_t k = 0; k < pending_loads.size(); k++) run_profile_load(pending_loads[k]);   // load_species_profile calls of begin_initialization
+  pending_loads.clear();
 }
 
 // ---- initialize: src/vpic/initialize.cxx:13-100 ----------------------------------------------------

@@ -405,6 +405,14 @@ public:
   };
   void collide(species_t *a, species_t *b, const collide_params_t &prm);
   int64_t particle_mirror_downloads(void) const;    // whole-species downloads into the host mirrors so far (diagnostics, tests)
+  int64_t particle_mirror_uploads(void) const;      // particles that went from a host mirror to the device so far
+  // A species loaded on the device from per-cell tables (vpic_hip_species_load_profile, include/vpic_hip.h: THE RULE, the
+  // flags, what is refused): what a deck's `repeat( n ) inject_particle( ... )` loop over a profile does, without a host
+  // record per particle.  The tables are this rank's own (tdim: 1 or the local grid's extent per axis); the host fills
+  // gdim and goff from its place in the decomposition, so every rank's particles are those of the uncut run.  Usable from
+  // begin_initialization (carried out when the run starts, behind the upload of what the deck injected on the host; the
+  // tables are copied) and from the hooks (carried out at once).  sp->np follows; sp->p goes stale, as after a push.
+  void load_species_profile(species_t *sp, const vpic_hip_load_t &d);
   bool resident_energy_f(double *en, const field_t *f);
 
 private:
@@ -423,6 +431,9 @@ private:
   std::vector<particle_t> injected_rhob;            // ... those whose charge, negated, goes to rhob (update_rhob)
   void flush_injected(void);
   void run_emitters(void);
+  struct profile_load_t { species_t *sp; vpic_hip_load_t d; std::vector<int32_t> count; std::vector<float> tab[7]; };   // q, ud x y z, uth x y z
+  std::vector<profile_load_t> pending_loads;        // load_species_profile calls made before the engine existed
+  void run_profile_load(const profile_load_t &l);
 public:
   int boundary_kind(int k) const;                   // of grid->boundary[k]: 0 maxwellian_reflux, 1 absorb_tally, 2 link_boundary
   int n_boundaries(int kind) const;

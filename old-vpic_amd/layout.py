@@ -46,6 +46,13 @@ wall_record_t = np.dtype([("dx", "f4"), ("dy", "f4"), ("dz", "f4"), ("i", "i4"),
 WALL_TALLY, WALL_RECORD, WALL_ROWS = 1, 2, 7
 assert wall_tally_t.itemsize == 40 and wall_record_t.itemsize == 56
 
+# the description of a load from per-cell tables (include/vpic_hip.h: vpic_hip_load_t; the tables as host addresses)
+load_t = np.dtype([("count", "u8"), ("q", "u8"), ("ud", "u8", (3,)), ("uth", "u8", (3,)), ("tdim", "i4", (3,)),
+                   ("gdim", "i8", (3,)), ("goff", "i8", (3,)), ("seed", "u4"), ("stream", "u4"), ("flags", "i4"),
+                   ("tag0", "i8")], align=True)
+LOAD_APPEND, LOAD_FLIP, LOAD_TAGS = 1, 2, 4
+assert load_t.itemsize == 152 and load_t.fields["gdim"][1] == 80 and load_t.fields["tag0"][1] == 144
+
 assert particle_t.itemsize == 48 and particle_mover_t.itemsize == 16 and particle_injector_t.itemsize == 48
 assert interpolator_t.itemsize == 80 and accumulator_t.itemsize == 48 and field_t.itemsize == 80
 assert material_coefficient_t.itemsize == 64
