@@ -6,8 +6,12 @@
 // (plan_distribution, plan_dist_tiles, plan_chunks); the window protocol, add_together, the check of the tile partition
 // and the statistics block are the ones every pass over a species uses (engine.h).
 // Behind the histograms: the per-bin sums of particle quantities (vpic_hip_species_distribution_sums), kernel instances of their
-// own over the same loads, coordinates and counted test; 64-bit integer sums, in LDS while they fit (policy.h, plan_distribution_sums).
+// own over the same loads and coordinates; 64-bit integer sums, in LDS while they fit (policy.h, plan_distribution_sums).
+// The counted test, the values of the sums, their LDS block and the statistics are hist_device.h's, which the cells'
+// histograms (cell_dist.hip) use too; both calls answer through Engine::species_hist (engine.h, HistResult), the counts-only
+// call through its counts and Engine::dist_stats.
 #include "dist_coords.h"
+#include "hist_device.h"
 #include <algorithm>
 
 namespace vpichip {
@@ -157,22 +161,12 @@ void species_distribution_kernel(ParticlesK p, long long np, long long chunk, Di
     }
     const bool kept = live && dist_in_ranges<FIELDS>(v, k.d.sel, k.d.n_sel);
     n_kept += __popcll(__ballot(kept));
-    bool counted = kept;
-    int b0 = 0, b1 = 0;
-    {
-      const double t0 = (dist_coord<FIELDS>(v, k.d.axis[0].coord) - k.d.axis[0].lo) / k.d.axis[0].d;
-      counted = counted && t0 >= 0.0 && t0 < (double)k.n0;
-      b0 = counted ? (int)t0 : 0;
-    }
-    if (k.d.n_axes == 2) {
-      const double t1 = (dist_coord<FIELDS>(v, k.d.axis[1].coord) - k.d.axis[1].lo) / k.d.axis[1].d;
-      counted = counted && t1 >= 0.0 && t1 < (double)k.n1;
-      b1 = counted ? (int)t1 : 0;
-    }
+    const HistBin h = hist_bin(kept, k.d, k.n0, k.n1, [&](int coord) { return dist_coord<FIELDS>(v, coord); });
+    const bool counted = h.counted;
     const unsigned long long counted_mask = __ballot(counted);
     n_counted += __popcll(counted_mask);
     if (!counted_mask) continue;
-    const int a_global = b1 * k.n0 + b0;                                     // (below VPIC_HIP_DIST_MAX_BINS)
+    const int a_global = h.a;                                                // (below VPIC_HIP_DIST_MAX_BINS)
 
     if (PATH == DIST_LDS) {
       add_together(s_dist, a_global, counted, lane);
@@ -180,7 +174,7 @@ void species_distribution_kernel(ParticlesK p, long long np, long long chunk, Di
       add_together(counts, a_global, counted, lane);
       n_miss += __popcll(counted_mask);
     } else {
-      const int pos = k.pos_axis == 0 ? b0 : b1, other = k.pos_axis == 0 ? b1 : b0;
+      const int pos = k.pos_axis == 0 ? h.b0 : h.b1, other = k.pos_axis == 0 ? h.b1 : h.b0;
       // the window goes to the bin in which the lowest tile still waiting begins
       const bool pending = window_add(w_state, win, k.win, k.n_other, pos, other, counted, lane,
         [&](unsigned long long left) {
@@ -201,12 +195,7 @@ void species_distribution_kernel(ParticlesK p, long long np, long long chunk, Di
   }
   }
   if (PATH == DIST_WINDOW && w_state.placed) flush_dist_window(win, w_state.base, k, counts, lane);
-  if (lane == 0 && n_seen) {
-    atomicAdd(&stats[0], n_seen);
-    if (n_kept) atomicAdd(&stats[1], n_kept);
-    if (n_counted) atomicAdd(&stats[2], n_counted);
-    if (n_miss) atomicAdd(&stats[3], n_miss);
-  }
+  hist_publish(stats, lane, n_seen, n_kept, n_counted, n_miss);
   if (PATH == DIST_LDS) {
     __syncthreads();
     for (int j = threadIdx.x; j < lds_words; j += 64 * DIST_WAVES)
@@ -214,8 +203,8 @@ void species_distribution_kernel(ParticlesK p, long long np, long long chunk, Di
   }
 }
 
-// the histogram of species s into Engine::dist_counts (device) and Engine::dist_host (pinned), after the stream has been
-// waited for
+// the histogram of species s into the counts of Engine::species_hist (which the sums' call fills too), its four statistics
+// into Engine::dist_stats, after the stream has been waited for
 int k_species_distribution(Engine *e, Species &s, const vpic_hip_dist_t &d) {
   DistK k{};
   k.d = d;
@@ -229,8 +218,9 @@ int k_species_distribution(Engine *e, Species &s, const vpic_hip_dist_t &d) {
   k.pos_axis = pl.pos_axis; k.win = pl.win; k.n_other = pl.n_other;
   const int path = pl.path;
   const size_t bins = (size_t)k.n0 * (size_t)k.n1;
-  if (grow(e->dist_counts, e->dist_bins, bins) || grow_pinned(e->dist_host, e->dist_host_bins, bins) || e->dist_stats.begin(e->stream)) return 1;
-  VH_CHECK(hipMemsetAsync(e->dist_counts, 0, bins * sizeof(unsigned long long), e->stream));
+  HistResult &h = e->species_hist;
+  if (h.grow_counts(bins) || e->dist_stats.begin(e->stream)) return 1;
+  VH_CHECK(hipMemsetAsync(h.counts, 0, bins * sizeof(unsigned long long), e->stream));
   if (s.np > 0) {
     const Chunks ch = plan_chunks(s.np, DIST_WAVES);
     long long nb = ch.groups;
@@ -256,22 +246,17 @@ int k_species_distribution(Engine *e, Species &s, const vpic_hip_dist_t &d) {
       : (path == DIST_LDS ? species_distribution_kernel<DIST_LDS, false>
          : path == DIST_WINDOW ? species_distribution_kernel<DIST_WINDOW, false> : species_distribution_kernel<DIST_GLOBAL, false>);
     hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(64 * DIST_WAVES), lds, e->stream, s.p, (long long)s.np, ch.chunk, k, tl, e->gk, tk,
-                       e->dist_counts, e->dist_stats.dev, (const vpic_interpolator_t *)e->fi);
+                       h.counts, e->dist_stats.dev, (const vpic_interpolator_t *)e->fi);
     VH_CHECK(hipGetLastError());
   }
-  VH_CHECK(hipMemcpyAsync(e->dist_host, e->dist_counts, bins * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+  VH_CHECK(hipMemcpyAsync(h.counts_host, h.counts, bins * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
   return e->dist_stats.read(e->stream);
 }
 
 // ---- per-bin sums of particle quantities (vpic_hip_species_distribution_sums; include/vpic_hip.h states the arithmetic) ----
-struct DistSumsK {
-  vpic_hip_dist_t d;
-  vpic_hip_dist_value_t v[VPIC_HIP_DIST_MAX_VALUES];
+struct DistSumsK : HistK {
   unsigned need, vneed;                        // need: as DistK::need, the factors' coordinates included; vneed: VAL_* (dist_coords.h)
-  int n0, n1, n_val;
 };
-
-// (SUMS_TOGETHER_MIN and add_sums_together, which the sums over the cells of the grid use too (cell_dist.hip): engine.h)
 
 // One pass over the species, every wavefront a contiguous chunk, as species_distribution_kernel walks it (the same loads
 // ahead, the same coordinates, the same counted test), plus q when a value names it.
@@ -288,11 +273,7 @@ void species_distribution_sums_kernel(ParticlesK p, long long np, long long chun
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int bins = k.n0 * k.n1;
   unsigned *s_counts = reinterpret_cast<unsigned *>(s_sums + k.n_val * bins);
-  if (PATH == DIST_LDS) {
-    for (int j = threadIdx.x; j < k.n_val * bins; j += 64 * DIST_WAVES) s_sums[j] = 0;
-    for (int j = threadIdx.x; j < bins; j += 64 * DIST_WAVES) s_counts[j] = 0;
-    __syncthreads();
-  }
+  if (PATH == DIST_LDS) hist_lds_clear<64 * DIST_WAVES>(s_sums, s_counts, k.n_val, bins);
   const long long w = (long long)blockIdx.x * DIST_WAVES + wave;
   const long long begin = w * chunk, end = begin + chunk < np ? begin + chunk : np;
   unsigned long long n_seen = 0, n_kept = 0, n_counted = 0, n_refused[VPIC_HIP_DIST_MAX_VALUES] = {0, 0, 0, 0};
@@ -327,83 +308,32 @@ void species_distribution_sums_kernel(ParticlesK p, long long np, long long chun
     }
     const bool kept = live && dist_in_ranges<FIELDS>(v, k.d.sel, k.d.n_sel);
     n_kept += __popcll(__ballot(kept));
-    bool counted = kept;
-    int b0 = 0, b1 = 0;
-    {
-      const double t0 = (dist_coord<FIELDS>(v, k.d.axis[0].coord) - k.d.axis[0].lo) / k.d.axis[0].d;
-      counted = counted && t0 >= 0.0 && t0 < (double)k.n0;
-      b0 = counted ? (int)t0 : 0;
-    }
-    if (k.d.n_axes == 2) {
-      const double t1 = (dist_coord<FIELDS>(v, k.d.axis[1].coord) - k.d.axis[1].lo) / k.d.axis[1].d;
-      counted = counted && t1 >= 0.0 && t1 < (double)k.n1;
-      b1 = counted ? (int)t1 : 0;
-    }
-    const unsigned long long counted_mask = __ballot(counted);
+    const HistBin h = hist_bin(kept, k.d, k.n0, k.n1, [&](int coord) { return dist_coord<FIELDS>(v, coord); });
+    const unsigned long long counted_mask = __ballot(h.counted);
     n_counted += __popcll(counted_mask);
     if (!counted_mask) continue;
-    const int a = b1 * k.n0 + b0;                                            // (below bins; 0 for a lane that is not counted)
-    if (PATH == DIST_LDS) add_together(s_counts, a, counted, lane);
-    else add_together(counts, a, counted, lane);
-
+    if (PATH == DIST_LDS) add_together(s_counts, h.a, h.counted, lane);
+    else add_together(counts, h.a, h.counted, lane);
     const DistExtra x = dist_extra<FIELDS>(r, f, q, v, k.vneed);
-    const int lead = __ffsll((long long)counted_mask) - 1;
-    const int a0 = __builtin_amdgcn_readlane(a, lead);
-    const unsigned long long same = __ballot(counted && a == a0);
-    const bool together = __popcll(same) >= SUMS_TOGETHER_MIN;
-#pragma unroll
-    for (int j = 0; j < VPIC_HIP_DIST_MAX_VALUES; j++) {
-      if (j >= k.n_val) break;
-      const vpic_hip_dist_value_t &val = k.v[j];
-      const double product = (dist_factor<FIELDS>(v, x, val.factor[0]) * dist_factor<FIELDS>(v, x, val.factor[1])) * dist_factor<FIELDS>(v, x, val.factor[2]);
-      const double tq = product / val.quantum;
-      const bool taken = counted && fabs(tq) < 4294967296.0;                 // (a NaN is refused)
-      n_refused[j] += __popcll(__ballot(counted && !taken));
-      const long long addend = taken ? llrint(tq) : 0;
-      if (PATH == DIST_LDS) add_sums_together(s_sums + j * bins, a, addend, taken, together, same, lead, lane);
-      else add_sums_together(sums + (size_t)j * bins, a, addend, taken, together, same, lead, lane);
-    }
+    hist_add_values(k, bins, h, counted_mask, [&](int code) { return dist_factor<FIELDS>(v, x, code); },
+                    PATH == DIST_LDS ? s_sums : sums, n_refused, lane);
   }
-  if (lane == 0 && n_seen) {
-    atomicAdd(&stats[0], n_seen);
-    if (n_kept) atomicAdd(&stats[1], n_kept);
-    if (n_counted) atomicAdd(&stats[2], n_counted);
-    if (PATH == DIST_GLOBAL && n_counted) atomicAdd(&stats[3], n_counted);
-#pragma unroll
-    for (int j = 0; j < VPIC_HIP_DIST_MAX_VALUES; j++)
-      if (n_refused[j]) atomicAdd(&stats[4 + j], n_refused[j]);
-  }
-  if (PATH == DIST_LDS) {
-    __syncthreads();
-    for (int j = threadIdx.x; j < bins; j += 64 * DIST_WAVES)
-      if (s_counts[j]) atomicAdd(&counts[j], (unsigned long long)s_counts[j]);
-    for (int j = threadIdx.x; j < k.n_val * bins; j += 64 * DIST_WAVES)
-      if (s_sums[j]) atomicAdd(&sums[j], s_sums[j]);
-  }
+  hist_publish(stats, lane, n_seen, n_kept, n_counted, PATH == DIST_GLOBAL ? n_counted : 0, n_refused);
+  if (PATH == DIST_LDS) hist_lds_flush<64 * DIST_WAVES>(s_sums, s_counts, k.n_val, bins, counts, sums);
 }
 
-// the histogram and the sums of species s into Engine::dist_counts / dist_host and dist_sums / dist_sums_host, the eight statistics
-// into dist_sums_last, after the stream has been waited for
+// the histogram, the sums and the eight statistics of species s into Engine::species_hist, after the stream has been waited for
 int k_species_distribution_sums(Engine *e, Species &s, const vpic_hip_dist_t &d, const vpic_hip_dist_value_t *v, int n_val) {
   DistSumsK k{};
-  k.d = d;
-  k.n0 = d.axis[0].n; k.n1 = d.n_axes == 2 ? d.axis[1].n : 1;
-  k.n_val = n_val;
+  fill_hist_k(k, d, v, n_val);
   for (int a = 0; a < d.n_axes; a++) k.need |= 1u << d.axis[a].coord;
   for (int r = 0; r < d.n_sel; r++) k.need |= 1u << d.sel[r].coord;
-  for (int j = 0; j < n_val; j++) {
-    k.v[j] = v[j];
+  for (int j = 0; j < n_val; j++)
     for (int c = 0; c < 3; c++) dist_factor_need(v[j].factor[c], k.need, k.vneed);
-  }
   const size_t bins = (size_t)k.n0 * (size_t)k.n1, words = bins * (size_t)n_val;
   const DistSumsPlan pl = plan_distribution_sums((long long)bins, n_val, VPIC_HIP_DIST_LDS_BINS);
-  if (grow(e->dist_counts, e->dist_bins, bins) || grow_pinned(e->dist_host, e->dist_host_bins, bins) ||
-      grow(e->dist_sums, e->dist_sums_words, words) || grow_pinned(e->dist_sums_host, e->dist_sums_host_words, words)) return 1;
-  if (!e->dist_sums_stats) VH_CHECK(hipMalloc((void **)&e->dist_sums_stats, DIST_SUMS_STATS * sizeof(unsigned long long)));
-  if (!e->dist_sums_stats_host) VH_CHECK(hipHostMalloc((void **)&e->dist_sums_stats_host, DIST_SUMS_STATS * sizeof(unsigned long long), hipHostMallocDefault));
-  VH_CHECK(hipMemsetAsync(e->dist_sums_stats, 0, DIST_SUMS_STATS * sizeof(unsigned long long), e->stream));
-  VH_CHECK(hipMemsetAsync(e->dist_counts, 0, bins * sizeof(unsigned long long), e->stream));
-  VH_CHECK(hipMemsetAsync(e->dist_sums, 0, words * sizeof(unsigned long long), e->stream));
+  HistResult &h = e->species_hist;
+  if (h.begin(bins, words, e->stream)) return 1;
   if (s.np > 0) {
     const Chunks ch = plan_chunks(s.np, DIST_WAVES);
     const size_t lds = sizeof(unsigned) * (size_t)pl.words;
@@ -411,15 +341,10 @@ int k_species_distribution_sums(Engine *e, Species &s, const vpic_hip_dist_t &d,
     auto kernel = fields ? (pl.path == DIST_LDS ? species_distribution_sums_kernel<DIST_LDS, true> : species_distribution_sums_kernel<DIST_GLOBAL, true>)
                          : (pl.path == DIST_LDS ? species_distribution_sums_kernel<DIST_LDS, false> : species_distribution_sums_kernel<DIST_GLOBAL, false>);
     hipLaunchKernelGGL(kernel, dim3((unsigned)ch.groups), dim3(64 * DIST_WAVES), lds, e->stream, s.p, (long long)s.np, ch.chunk, k, e->gk,
-                       make_tile_k(e->gk), e->dist_counts, e->dist_sums, e->dist_sums_stats, (const vpic_interpolator_t *)e->fi);
+                       make_tile_k(e->gk), h.counts, h.sums, h.stats.dev, (const vpic_interpolator_t *)e->fi);
     VH_CHECK(hipGetLastError());
   }
-  VH_CHECK(hipMemcpyAsync(e->dist_host, e->dist_counts, bins * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-  VH_CHECK(hipMemcpyAsync(e->dist_sums_host, e->dist_sums, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-  VH_CHECK(hipMemcpyAsync(e->dist_sums_stats_host, e->dist_sums_stats, DIST_SUMS_STATS * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-  VH_CHECK(hipStreamSynchronize(e->stream));
-  for (int j = 0; j < DIST_SUMS_STATS; j++) e->dist_sums_last[j] = (int64_t)e->dist_sums_stats_host[j];
-  return 0;
+  return h.read(bins, words, e->stream);
 }
 
 }  // namespace vpichip

@@ -291,29 +291,65 @@ inline int grow(T *&buf, size_t &have, size_t want) {
 }
 template <typename T> inline int grow_pinned(T *&buf, size_t &have, size_t want) { return grow<T, true>(buf, have, want); }
 
-// The statistics of a diagnostic's last call: up to four 64-bit words its kernels add to on the device, the pinned words they
-// come back through, and what was read.  Word STATS_BAD_PARTITION is k_check_tile_partition's flag (never read back).
-constexpr int STATS_WORDS = 4, STATS_BAD_PARTITION = 4;
+// The statistics of a diagnostic's last call: WORDS 64-bit words its kernels add to on the device (four; eight for the
+// per-bin sums), the pinned words they come back through, and what was read.  One word more, behind them, is
+// k_check_tile_partition's flag (never read back).
+template <int WORDS>
 struct DiagStats {
   unsigned long long *dev = nullptr, *host = nullptr;
-  int64_t last[STATS_WORDS] = {0, 0, 0, 0};
+  int64_t last[WORDS] = {};
   bool pending = false;              // a caller that defers its read (moments.hip) says so here
   // before a call's kernels: allocated by the first call, zeroed on the stream
   int begin(hipStream_t stream) {
-    if (!dev) VH_CHECK(hipMalloc((void **)&dev, (STATS_WORDS + 1) * sizeof(unsigned long long)));
-    if (!host) VH_CHECK(hipHostMalloc((void **)&host, STATS_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
-    VH_CHECK(hipMemsetAsync(dev, 0, (STATS_WORDS + 1) * sizeof(unsigned long long), stream));
+    if (!dev) VH_CHECK(hipMalloc((void **)&dev, (WORDS + 1) * sizeof(unsigned long long)));
+    if (!host) VH_CHECK(hipHostMalloc((void **)&host, WORDS * sizeof(unsigned long long), hipHostMallocDefault));
+    VH_CHECK(hipMemsetAsync(dev, 0, (WORDS + 1) * sizeof(unsigned long long), stream));
     return 0;
   }
   // behind them: copied, the stream waited for, last[] filled
   int read(hipStream_t stream) {
-    VH_CHECK(hipMemcpyAsync(host, dev, STATS_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    VH_CHECK(hipMemcpyAsync(host, dev, WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     VH_CHECK(hipStreamSynchronize(stream));
-    for (int j = 0; j < STATS_WORDS; j++) last[j] = (int64_t)host[j];
+    for (int j = 0; j < WORDS; j++) last[j] = (int64_t)host[j];
     pending = false;
     return 0;
   }
-  unsigned *bad_partition() const { return reinterpret_cast<unsigned *>(dev + STATS_BAD_PARTITION); }
+  unsigned *bad_partition() const { return reinterpret_cast<unsigned *>(dev + WORDS); }
+  void release() { (void)hipFree(dev); (void)hipHostFree(host); dev = host = nullptr; }
+};
+
+// The result of a histogram with per-bin sums (distribution.hip: one for the species; cell_dist.hip: one for the cells),
+// allocated by the first call and grown on demand: the 64-bit counts and the n_val rows of 64-bit sums on the device, the
+// pinned buffers they come back through (each as long as its device twin), and the statistics {seen, kept, counted,
+// through global memory, refused for value 0 .. 3}.
+struct HistResult {
+  unsigned long long *counts = nullptr, *counts_host = nullptr, *sums = nullptr, *sums_host = nullptr;
+  size_t bins = 0, words = 0;        // what counts / counts_host and sums / sums_host hold
+  DiagStats<8> stats;
+  static int grow_pair(unsigned long long *&dev, unsigned long long *&host, size_t &have, size_t want) {
+    size_t dev_have = have;
+    return grow(dev, dev_have, want) || grow_pinned(host, have, want);
+  }
+  int grow_counts(size_t n_bins) { return grow_pair(counts, counts_host, bins, n_bins); }
+  int grow_sums(size_t n_words) { return grow_pair(sums, sums_host, words, n_words); }
+  // before a call's kernel: room for n_bins counts and n_words sums, then statistics, counts and sums zeroed on the stream
+  int begin(size_t n_bins, size_t n_words, hipStream_t stream) {
+    if (grow_counts(n_bins) || grow_sums(n_words) || stats.begin(stream)) return 1;
+    VH_CHECK(hipMemsetAsync(counts, 0, n_bins * sizeof(unsigned long long), stream));
+    if (n_words) VH_CHECK(hipMemsetAsync(sums, 0, n_words * sizeof(unsigned long long), stream));
+    return 0;
+  }
+  // behind it: counts, sums and statistics copied, the stream waited for, stats.last[] filled
+  int read(size_t n_bins, size_t n_words, hipStream_t stream) {
+    VH_CHECK(hipMemcpyAsync(counts_host, counts, n_bins * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    if (n_words) VH_CHECK(hipMemcpyAsync(sums_host, sums, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    return stats.read(stream);
+  }
+  void release() {
+    (void)hipFree(counts); (void)hipHostFree(counts_host); (void)hipFree(sums); (void)hipHostFree(sums_host);
+    counts = counts_host = sums = sums_host = nullptr; bins = words = 0;
+    stats.release();
+  }
 };
 
 struct Engine {
@@ -384,35 +420,26 @@ struct Engine {
   // (n_lin x nv), the log bins and the pinned words they come back through; statistics {particles counted, window misses}
   unsigned *spec_lin = nullptr; float *spec_bands = nullptr; size_t spec_lin_words = 0;   // (spec_bands is as long as spec_lin)
   unsigned long long *spec_log = nullptr, *spec_log_host = nullptr;                          // VPIC_HIP_SPECTRUM_MAX_LOG words each
-  DiagStats spec_stats;
-  // phase-space distributions (distribution.hip), allocated by the first call and grown on demand: the counters and the
-  // pinned buffer they come back through; statistics {seen, kept, counted, misses}
-  unsigned long long *dist_counts = nullptr, *dist_host = nullptr; size_t dist_bins = 0, dist_host_bins = 0;
-  DiagStats dist_stats;
-  // ... and the per-bin sums beside them (vpic_hip_species_distribution_sums), allocated by the first call and grown on
-  // demand: n_val rows of 64-bit sums and the pinned buffer they come back through; statistics {seen, kept, counted,
-  // through global memory, refused for value 0 .. 3} on the device, pinned, and as read by the last call
-  unsigned long long *dist_sums = nullptr, *dist_sums_host = nullptr; size_t dist_sums_words = 0, dist_sums_host_words = 0;
-  unsigned long long *dist_sums_stats = nullptr, *dist_sums_stats_host = nullptr; int64_t dist_sums_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  // cell distributions (cell_dist.hip), allocated by the first call and grown on demand: the counters and the n_val rows of
-  // 64-bit sums over the cells of the grid, the pinned buffers they come back through; statistics {seen, kept, counted,
-  // through global memory, refused for value 0 .. 3} on the device, pinned, and as read by the last call (eight words, as
-  // the species' sums keep theirs: a DiagStats holds four)
-  unsigned long long *cell_counts = nullptr, *cell_host = nullptr; size_t cell_bins = 0, cell_host_bins = 0;
-  unsigned long long *cell_sums = nullptr, *cell_sums_host = nullptr; size_t cell_sums_words = 0, cell_sums_host_words = 0;
-  unsigned long long *cell_stats = nullptr, *cell_stats_host = nullptr; int64_t cell_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  DiagStats<4> spec_stats;
+  // phase-space distributions of a species and the per-bin sums beside them (distribution.hip): one result block.  The
+  // counts-only call (vpic_hip_species_distribution) writes into its counts too and keeps statistics of its own, {seen,
+  // kept, counted, misses}, so that a sums call leaves them alone
+  HistResult species_hist;
+  DiagStats<4> dist_stats;
+  // cell distributions (cell_dist.hip): the same over the cells of the grid
+  HistResult cell_hist;
   // hydro moments and rho summed by tile (moments.hip), allocated by the first call: the fixed-point words of the
   // deterministic hydro sums (14 per voxel, zero between calls); statistics {live, through LDS, through global memory, out
   // of range} (mom_stats.pending: the last call's are still on the device, not read yet)
   unsigned long long *hydro64 = nullptr;
-  DiagStats mom_stats;
+  DiagStats<4> mom_stats;
   // selected particles (select.hip), allocated by the first call and grown on demand: one keep bit per particle, the
   // kept count and the 64-bit offset of every chunk, the device output arrays (records, six floats per record, indices);
   // statistics {live particles seen, kept, written, chunks}
   unsigned long long *sel_mask = nullptr, *sel_offsets = nullptr; unsigned *sel_counts = nullptr;
   size_t sel_mask_n = 0, sel_offsets_n = 0, sel_counts_n = 0;
   vpic_particle_t *sel_p = nullptr; float *sel_f = nullptr; int64_t *sel_i = nullptr; size_t sel_p_n = 0, sel_f_n = 0, sel_i_n = 0;
-  DiagStats sel_stats;
+  DiagStats<4> sel_stats;
 
   // binary collisions (collide.hip), allocated by the first call: the test mode's draws (4 floats per particle index), the
   // words its kernels write on the device and the pinned words they come back through (COLLIDE_WORDS), what the last call
@@ -506,11 +533,9 @@ int k_energy_p(Engine *e, Species &s, double *energy);
 int k_center_p(Engine *e, Species &s, bool uncenter);
 int k_energy_spectrum(Engine *e, Species &s, const vpic_hip_spectrum_t &sp);   // into Engine::spec_lin / spec_log / spec_log_host; waits for the stream
 int k_energy_bands(Engine *e, int n_lin);                                        // Engine::spec_lin -> spec_bands
-int k_species_distribution(Engine *e, Species &s, const vpic_hip_dist_t &d);     // into Engine::dist_counts / dist_host; waits for the stream
-constexpr int DIST_SUMS_STATS = 8;       // words of Engine::dist_sums_stats
-int k_species_distribution_sums(Engine *e, Species &s, const vpic_hip_dist_t &d, const vpic_hip_dist_value_t *v, int n_val);   // ... and into dist_sums / dist_sums_host
-constexpr int CELL_DIST_STATS = 8;       // words of Engine::cell_stats
-int k_cell_distribution(Engine *e, const vpic_hip_dist_t &d, const vpic_hip_dist_value_t *v, int n_val);   // cell_dist.hip: into Engine::cell_counts / cell_host, cell_sums / cell_sums_host; waits for the stream
+int k_species_distribution(Engine *e, Species &s, const vpic_hip_dist_t &d);     // into the counts of Engine::species_hist and dist_stats; waits for the stream
+int k_species_distribution_sums(Engine *e, Species &s, const vpic_hip_dist_t &d, const vpic_hip_dist_value_t *v, int n_val);   // ... into all of species_hist
+int k_cell_distribution(Engine *e, const vpic_hip_dist_t &d, const vpic_hip_dist_value_t *v, int n_val);   // cell_dist.hip: into Engine::cell_hist; waits for the stream
 // select.hip: launches 1 and 2 (count_only: no masks), and launch 3 into Engine::sel_p / sel_f / sel_i where asked for; waits for the stream
 int k_species_select(Engine *e, Species &s, const vpic_hip_select_t &d, int64_t cap, bool want_p, bool want_f, bool want_i, bool count_only);
 // collide.hip: the checking pass, the sorts it asks for, the launch; wants_tile_a / _b: the order a sort of that species would produce now;

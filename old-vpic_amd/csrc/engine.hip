@@ -201,13 +201,10 @@ static void destroy(Engine *e) {
   (void)hipFree(e->retry_buf); (void)hipFree(e->tile_list[0]); (void)hipFree(e->tile_list[1]);
   (void)hipFree(e->acc64); (void)hipFree(e->rho64);
   (void)hipFree(e->spec_lin); (void)hipFree(e->spec_bands); (void)hipFree(e->spec_log); (void)hipHostFree(e->spec_log_host);
-  (void)hipFree(e->dist_counts); (void)hipHostFree(e->dist_host); (void)hipFree(e->hydro64);
-  (void)hipFree(e->cell_counts); (void)hipHostFree(e->cell_host); (void)hipFree(e->cell_sums); (void)hipHostFree(e->cell_sums_host);
-  (void)hipFree(e->cell_stats); (void)hipHostFree(e->cell_stats_host);
-  (void)hipFree(e->dist_sums); (void)hipHostFree(e->dist_sums_host); (void)hipFree(e->dist_sums_stats); (void)hipHostFree(e->dist_sums_stats_host);
+  e->species_hist.release(); e->cell_hist.release(); (void)hipFree(e->hydro64);
   (void)hipFree(e->sel_mask); (void)hipFree(e->sel_offsets); (void)hipFree(e->sel_counts);
   (void)hipFree(e->sel_p); (void)hipFree(e->sel_f); (void)hipFree(e->sel_i);
-  for (DiagStats *st : {&e->spec_stats, &e->dist_stats, &e->mom_stats, &e->sel_stats}) { (void)hipFree(st->dev); (void)hipHostFree(st->host); }
+  for (DiagStats<4> *st : {&e->spec_stats, &e->dist_stats, &e->mom_stats, &e->sel_stats}) st->release();
   for (auto &ev : e->ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
   for (auto ev : e->step_done) if (ev) (void)hipEventDestroy(ev);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -823,10 +820,11 @@ static int check_range_count(const char *what, int n_sel) {
 static bool known_coord(int c) {
   return (c >= VPIC_HIP_COORD_X && c <= VPIC_HIP_COORD_LOG10_KE) || (c >= VPIC_HIP_COORD_U_PAR && c <= VPIC_HIP_COORD_E_PAR);
 }
-static int check_ranges(const char *what, const vpic_hip_dist_range_t *sel, int n_sel) {
+// known: the codes a range may name (a particle's coordinates; a cell's, cell_coords.h)
+static int check_ranges(const char *what, const vpic_hip_dist_range_t *sel, int n_sel, bool (*known)(int) = known_coord) {
   if (check_range_count(what, n_sel)) return 1;
   for (int r = 0; r < n_sel; r++)
-    if (!known_coord(sel[r].coord)) VH_FAIL("%s: unknown coordinate %d of range %d", what, sel[r].coord, r);
+    if (!known(sel[r].coord)) VH_FAIL("%s: unknown coordinate %d of range %d", what, sel[r].coord, r);
   return 0;
 }
 static int check_spectrum(const vpic_hip_spectrum_t *s, bool need_lin) {
@@ -866,111 +864,90 @@ int vpic_hip_energy_bands(vpic_hip_engine_t *e, int sp, const vpic_hip_spectrum_
   return 0;
 }
 // the first n statistics of a diagnostic's last call
-static int copy_stats(const DiagStats &st, int64_t *out, int n) {
+static int copy_stats(const int64_t *last, int64_t *out, int n) {
   if (!out) VH_FAIL("Bad output");
-  for (int j = 0; j < n; j++) out[j] = st.last[j];
+  for (int j = 0; j < n; j++) out[j] = last[j];
   return 0;
 }
-int vpic_hip_energy_spectrum_stats(vpic_hip_engine_t *e, int64_t out[2]) { ENGINE(e); return copy_stats(e->spec_stats, out, 2); }
-// a distribution's descriptor; bins: n0 * n1
-static int check_distribution(const vpic_hip_dist_t *d, long long &bins) {
-  if (!d) VH_FAIL("Bad distribution descriptor");
-  if (d->n_axes != 1 && d->n_axes != 2) VH_FAIL("distribution: %d axes (1 or 2)", d->n_axes);
-  if (check_range_count("distribution", d->n_sel)) return 1;   // (the order of the checks: count, axes, the ranges' coordinates)
+int vpic_hip_energy_spectrum_stats(vpic_hip_engine_t *e, int64_t out[2]) { ENGINE(e); return copy_stats(e->spec_stats.last, out, 2); }
+// The descriptor (not null) of a histogram, of a species or of the cells: `what` names the caller in the messages, `known`
+// is true of the codes an axis or a range may name; bins: n0 * n1
+static int check_distribution(const char *what, bool (*known)(int), const vpic_hip_dist_t *d, long long &bins) {
+  if (d->n_axes != 1 && d->n_axes != 2) VH_FAIL("%s: %d axes (1 or 2)", what, d->n_axes);
+  if (check_range_count(what, d->n_sel)) return 1;          // (the order of the checks: count, axes, the ranges' coordinates)
   bins = 1;
   for (int a = 0; a < d->n_axes; a++) {
     const vpic_hip_dist_axis_t &x = d->axis[a];
-    if (!known_coord(x.coord)) VH_FAIL("distribution: unknown coordinate %d of axis %d", x.coord, a);
-    if (x.n < 1) VH_FAIL("distribution: %d bins on axis %d", x.n, a);
-    if (!(x.d > 0) || !std::isfinite(x.d)) VH_FAIL("distribution: bin width %g of axis %d", x.d, a);
+    if (!known(x.coord)) VH_FAIL("%s: unknown coordinate %d of axis %d", what, x.coord, a);
+    if (x.n < 1) VH_FAIL("%s: %d bins on axis %d", what, x.n, a);
+    if (!(x.d > 0) || !std::isfinite(x.d)) VH_FAIL("%s: bin width %g of axis %d", what, x.d, a);
     bins *= x.n;                                            // (at most 2^62)
   }
-  if (check_ranges("distribution", d->sel, d->n_sel)) return 1;
-  if (bins > VPIC_HIP_DIST_MAX_BINS) VH_FAIL("distribution: %lld bins above the cap of %d", bins, VPIC_HIP_DIST_MAX_BINS);
+  if (check_ranges(what, d->sel, d->n_sel, known)) return 1;
+  if (bins > VPIC_HIP_DIST_MAX_BINS) VH_FAIL("%s: %lld bins above the cap of %d", what, bins, VPIC_HIP_DIST_MAX_BINS);
   return 0;
+}
+// ... and the values of its per-bin sums, `lowest` to VPIC_HIP_DIST_MAX_VALUES of them, with the array the sums go to;
+// known_factor is true of the codes a factor may name
+static int check_values(const char *what, bool (*known_factor)(int), int lowest, const vpic_hip_dist_value_t *v, int n_val, const int64_t *sums) {
+  if (n_val < lowest || n_val > VPIC_HIP_DIST_MAX_VALUES) VH_FAIL("%s: %d values (%d to %d)", what, n_val, lowest, VPIC_HIP_DIST_MAX_VALUES);
+  if (n_val > 0 && !v) VH_FAIL("Bad values array");
+  if (n_val > 0 && !sums) VH_FAIL("Bad sums array");
+  for (int k = 0; k < n_val; k++) {
+    for (int c = 0; c < 3; c++)
+      if (!known_factor(v[k].factor[c])) VH_FAIL("%s: factor %d of value %d is %d, not a factor", what, c, k, v[k].factor[c]);
+    if (!(v[k].quantum > 0) || !std::isfinite(v[k].quantum)) VH_FAIL("%s: quantum %g of value %d", what, v[k].quantum, k);
+  }
+  return 0;
+}
+// a factor of a species' sums: a coordinate but LOG10_KE, or one of VPIC_HIP_FACTOR_*
+static bool known_factor(int f) {
+  return (known_coord(f) && f != VPIC_HIP_COORD_LOG10_KE) || (f >= VPIC_HIP_FACTOR_ONE && f <= VPIC_HIP_FACTOR_EPAR_VPAR);
 }
 int vpic_hip_species_distribution(vpic_hip_engine_t *e, int sp, const vpic_hip_dist_t *d, uint64_t *counts) {
   ENGINE(e); SPECIES(e, sp);
-  if (d && !counts) VH_FAIL("Bad counts array");
+  if (!d) VH_FAIL("Bad distribution descriptor");
+  if (!counts) VH_FAIL("Bad counts array");
   long long bins = 0;
-  if (check_distribution(d, bins)) return 1;
+  if (check_distribution("distribution", known_coord, d, bins)) return 1;
   const size_t bytes = sizeof(uint64_t) * (size_t)bins;
   host_will_write(counts, bytes);
   if (k_species_distribution(e, e->species[sp], *d)) return 1;
-  memcpy(counts, e->dist_host, bytes);
+  memcpy(counts, e->species_hist.counts_host, bytes);
   return 0;
 }
-int vpic_hip_species_distribution_stats(vpic_hip_engine_t *e, int64_t out[4]) { ENGINE(e); return copy_stats(e->dist_stats, out, 4); }
+int vpic_hip_species_distribution_stats(vpic_hip_engine_t *e, int64_t out[4]) { ENGINE(e); return copy_stats(e->dist_stats.last, out, 4); }
 int vpic_hip_species_distribution_sums(vpic_hip_engine_t *e, int sp, const vpic_hip_dist_t *d, const vpic_hip_dist_value_t *v, int n_val,
                                        uint64_t *counts, int64_t *sums) {
   ENGINE(e); SPECIES(e, sp);
+  if (!d) VH_FAIL("Bad distribution descriptor");
   long long bins = 0;
-  if (check_distribution(d, bins)) return 1;
-  if (n_val < 1 || n_val > VPIC_HIP_DIST_MAX_VALUES) VH_FAIL("distribution sums: %d values (1 to %d)", n_val, VPIC_HIP_DIST_MAX_VALUES);
-  if (!v) VH_FAIL("Bad values array");
-  if (!sums) VH_FAIL("Bad sums array");
-  for (int k = 0; k < n_val; k++) {
-    for (int c = 0; c < 3; c++) {
-      const int f = v[k].factor[c];
-      const bool known = (known_coord(f) && f != VPIC_HIP_COORD_LOG10_KE) || (f >= VPIC_HIP_FACTOR_ONE && f <= VPIC_HIP_FACTOR_EPAR_VPAR);
-      if (!known) VH_FAIL("distribution sums: factor %d of value %d is %d, not a factor", c, k, f);
-    }
-    if (!(v[k].quantum > 0) || !std::isfinite(v[k].quantum)) VH_FAIL("distribution sums: quantum %g of value %d", v[k].quantum, k);
-  }
+  if (check_distribution("distribution", known_coord, d, bins) || check_values("distribution sums", known_factor, 1, v, n_val, sums)) return 1;
   const size_t count_bytes = sizeof(uint64_t) * (size_t)bins, sum_bytes = count_bytes * (size_t)n_val;
   if (counts) host_will_write(counts, count_bytes);
   host_will_write(sums, sum_bytes);
   if (k_species_distribution_sums(e, e->species[sp], *d, v, n_val)) return 1;
-  if (counts) memcpy(counts, e->dist_host, count_bytes);
-  memcpy(sums, e->dist_sums_host, sum_bytes);
+  if (counts) memcpy(counts, e->species_hist.counts_host, count_bytes);
+  memcpy(sums, e->species_hist.sums_host, sum_bytes);
   return 0;
 }
-int vpic_hip_species_distribution_sums_stats(vpic_hip_engine_t *e, int64_t out[8]) {
-  ENGINE(e);
-  if (!out) VH_FAIL("Bad output");
-  for (int j = 0; j < DIST_SUMS_STATS; j++) out[j] = e->dist_sums_last[j];
-  return 0;
-}
+int vpic_hip_species_distribution_sums_stats(vpic_hip_engine_t *e, int64_t out[8]) { ENGINE(e); return copy_stats(e->species_hist.stats.last, out, 8); }
 // ---- cell distributions (cell_dist.hip): the checks of the two calls above over the VPIC_HIP_CELL_* codes (cell_coords.h) ----
 int vpic_hip_cell_distribution(vpic_hip_engine_t *e, const vpic_hip_dist_t *d, const vpic_hip_dist_value_t *v, int n_val,
                                uint64_t *counts, int64_t *sums) {
   ENGINE(e);
   if (!d) VH_FAIL("Bad cell distribution descriptor");
   if (!counts && !sums) VH_FAIL("cell distribution: no output array");
-  if (d->n_axes != 1 && d->n_axes != 2) VH_FAIL("cell distribution: %d axes (1 or 2)", d->n_axes);
-  if (check_range_count("cell distribution", d->n_sel)) return 1;
-  long long bins = 1;
-  for (int a = 0; a < d->n_axes; a++) {
-    const vpic_hip_dist_axis_t &x = d->axis[a];
-    if (!cell_known_coord(x.coord)) VH_FAIL("cell distribution: unknown coordinate %d of axis %d", x.coord, a);
-    if (x.n < 1) VH_FAIL("cell distribution: %d bins on axis %d", x.n, a);
-    if (!(x.d > 0) || !std::isfinite(x.d)) VH_FAIL("cell distribution: bin width %g of axis %d", x.d, a);
-    bins *= x.n;                                            // (at most 2^62)
-  }
-  for (int r = 0; r < d->n_sel; r++)
-    if (!cell_known_coord(d->sel[r].coord)) VH_FAIL("cell distribution: unknown coordinate %d of range %d", d->sel[r].coord, r);
-  if (bins > VPIC_HIP_DIST_MAX_BINS) VH_FAIL("cell distribution: %lld bins above the cap of %d", bins, VPIC_HIP_DIST_MAX_BINS);
-  if (n_val < 0 || n_val > VPIC_HIP_DIST_MAX_VALUES) VH_FAIL("cell distribution: %d values (0 to %d)", n_val, VPIC_HIP_DIST_MAX_VALUES);
+  long long bins = 0;
+  if (check_distribution("cell distribution", cell_known_coord, d, bins) || check_values("cell distribution", cell_known_factor, 0, v, n_val, sums)) return 1;
   if (n_val == 0 && !counts) VH_FAIL("Bad counts array");
-  if (n_val > 0 && !v) VH_FAIL("Bad values array");
-  if (n_val > 0 && !sums) VH_FAIL("Bad sums array");
-  for (int k = 0; k < n_val; k++) {
-    for (int c = 0; c < 3; c++)
-      if (!cell_known_factor(v[k].factor[c])) VH_FAIL("cell distribution: factor %d of value %d is %d, not a factor", c, k, v[k].factor[c]);
-    if (!(v[k].quantum > 0) || !std::isfinite(v[k].quantum)) VH_FAIL("cell distribution: quantum %g of value %d", v[k].quantum, k);
-  }
   if (k_cell_distribution(e, *d, v, n_val)) return 1;       // (fails, before it launches, on a hydro code without a hydro array)
   const size_t count_bytes = sizeof(uint64_t) * (size_t)bins, sum_bytes = count_bytes * (size_t)n_val;
-  if (counts) { host_will_write(counts, count_bytes); memcpy(counts, e->cell_host, count_bytes); }
-  if (n_val > 0) { host_will_write(sums, sum_bytes); memcpy(sums, e->cell_sums_host, sum_bytes); }
+  if (counts) { host_will_write(counts, count_bytes); memcpy(counts, e->cell_hist.counts_host, count_bytes); }
+  if (n_val > 0) { host_will_write(sums, sum_bytes); memcpy(sums, e->cell_hist.sums_host, sum_bytes); }
   return 0;
 }
-int vpic_hip_cell_distribution_stats(vpic_hip_engine_t *e, int64_t out[8]) {
-  ENGINE(e);
-  if (!out) VH_FAIL("Bad output");
-  for (int j = 0; j < CELL_DIST_STATS; j++) out[j] = e->cell_last[j];
-  return 0;
-}
+int vpic_hip_cell_distribution_stats(vpic_hip_engine_t *e, int64_t out[8]) { ENGINE(e); return copy_stats(e->cell_hist.stats.last, out, 8); }
 static int check_select(const vpic_hip_select_t *s) {
   if (!s) VH_FAIL("Bad select descriptor");
   if (check_ranges("select", s->sel, s->n_sel)) return 1;
@@ -1003,7 +980,7 @@ int vpic_hip_species_select(vpic_hip_engine_t *e, int sp, const vpic_hip_select_
   if (n && index && copy_out(e, index, e->sel_i, sizeof(int64_t) * n)) return 1;
   return 0;
 }
-int vpic_hip_species_select_stats(vpic_hip_engine_t *e, int64_t out[4]) { ENGINE(e); return copy_stats(e->sel_stats, out, 4); }
+int vpic_hip_species_select_stats(vpic_hip_engine_t *e, int64_t out[4]) { ENGINE(e); return copy_stats(e->sel_stats.last, out, 4); }
 int vpic_hip_center_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp); return k_center_p(e, e->species[sp], false); }
 int vpic_hip_uncenter_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp); return k_center_p(e, e->species[sp], true); }
 int vpic_hip_clear_jf(vpic_hip_engine_t *e) { ENGINE(e); return k_clear_jf(e); }
