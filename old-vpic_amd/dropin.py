@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import layout as L
-from ._lib import lib
+from ._lib import SIGNATURES, lib
 
 
 class RefGrid(C.Structure):
@@ -79,47 +79,11 @@ def reference_grid(nx, ny, nz, lx, ly, lz, dt, cvac=1.0, eps0=1.0, damp=0.0, fbc
 
 
 def ref():
-    """The library with argument types of the drop-in entry points set."""
-    l = lib()
-    l.vpic_hip_ref_advance_p.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    l.vpic_hip_ref_advance_p.restype = C.c_int
-    l.vpic_hip_ref_energy_p.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
-    l.vpic_hip_ref_energy_p.restype = C.c_double
-    l.vpic_hip_ref_advance_b.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
-    for n in ("load_interpolator", "unload_accumulator", "advance_e", "energy_f"):
-        getattr(l, "vpic_hip_ref_" + n).argtypes = [C.c_void_p] * 3 if n != "energy_f" else [C.c_void_p] * 4
-    for n in ("clear_accumulators", "reduce_accumulators", "clear_jf", "synchronize_jf", "sort_p", "clear_rhof", "synchronize_rho",
-              "synchronize_tang_e_norm_b", "compute_rms_div_e_err", "compute_div_b_err", "compute_rms_div_b_err", "clean_div_b"):
-        getattr(l, "vpic_hip_ref_" + n).argtypes = [C.c_void_p] * 2
-    for n in ("compute_rhob", "compute_curl_b", "compute_div_e_err", "clean_div_e"):
-        getattr(l, "vpic_hip_ref_" + n).argtypes = [C.c_void_p] * 3
-    l.vpic_hip_ref_move_p.argtypes = [C.c_void_p] * 4
-    l.vpic_hip_ref_move_p.restype = C.c_int
-    l.vpic_hip_ref_boundary_p.argtypes = [C.c_void_p] * 5
-    for n in ("clear_hydro", "synchronize_hydro", "local_adjust_hydro"):
-        getattr(l, "vpic_hip_ref_" + n).argtypes = [C.c_void_p] * 2
-    l.vpic_hip_ref_accumulate_hydro_p.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
-    l.vpic_hip_ref_accumulate_rho_p.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    l.vpic_hip_ref_accumulate_rhob.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    for n in ("synchronize_tang_e_norm_b", "compute_rms_div_e_err", "compute_rms_div_b_err"):
-        getattr(l, "vpic_hip_ref_" + n).restype = C.c_double
-    return l
+    """The library; lib() has given the drop-in entry points their signatures from the header as well."""
+    return lib()
 
 
-DROPIN_EXPORTS = """vpic_hip_ref_set_transport vpic_hip_ref_set_accumulator_copies vpic_hip_ref_set_material_count vpic_hip_ref_load_interpolator
-vpic_hip_ref_clear_accumulators vpic_hip_ref_reduce_accumulators vpic_hip_ref_unload_accumulator
-vpic_hip_ref_advance_p vpic_hip_ref_energy_p vpic_hip_ref_center_p vpic_hip_ref_uncenter_p vpic_hip_ref_sort_p vpic_hip_ref_advance_b vpic_hip_ref_advance_e
-vpic_hip_ref_clear_jf vpic_hip_ref_synchronize_jf vpic_hip_ref_energy_f
-vpic_hip_ref_clear_rhof vpic_hip_ref_accumulate_rhob vpic_hip_ref_accumulate_rho_p vpic_hip_ref_synchronize_rho vpic_hip_ref_compute_rhob
-vpic_hip_ref_compute_curl_b vpic_hip_ref_synchronize_tang_e_norm_b vpic_hip_ref_compute_div_e_err
-vpic_hip_ref_compute_rms_div_e_err vpic_hip_ref_clean_div_e vpic_hip_ref_compute_div_b_err
-vpic_hip_ref_compute_rms_div_b_err vpic_hip_ref_clean_div_b
-vpic_hip_ref_move_p vpic_hip_ref_boundary_p vpic_hip_ref_clear_hydro vpic_hip_ref_accumulate_hydro_p
-vpic_hip_ref_synchronize_hydro vpic_hip_ref_local_adjust_hydro
-vpic_hip_ref_new_field vpic_hip_ref_delete_field vpic_hip_ref_new_material_coefficients
-vpic_hip_ref_delete_material_coefficients vpic_hip_ref_new_hydro vpic_hip_ref_delete_hydro
-vpic_hip_ref_new_interpolator vpic_hip_ref_delete_interpolator vpic_hip_ref_new_accumulators
-vpic_hip_ref_delete_accumulators""".split()
+DROPIN_EXPORTS = sorted(SIGNATURES["vpic_hip_dropin.h"])
 # field_advance_methods_t, slot by slot (src/field_advance/field_advance.h:185-302): the data symbol
 # vpic_hip_ref_field_advance_methods holds these entry points in this order
 FIELD_ADVANCE_SLOTS = """new_field delete_field new_material_coefficients delete_material_coefficients advance_b advance_e

@@ -86,34 +86,6 @@ CELL_COORDS.update({name: 113 + k for k, name in enumerate(("e_c", "b_c", "e_par
 CELL_FACTORS = {"one": 127}                                                                     # VPIC_HIP_CELL_ONE
 
 
-def cell_dist_desc(axes, select=()):
-    """vpic_hip_dist_t of one or two (coord, lo, d, n) axes and up to four (coord, lo, hi) ranges over the coordinates of a
-    cell, by name (KeyError for an unknown one, "one" included: it is a factor only)."""
-    axes, select = list(axes), list(select)
-    if len(axes) not in (1, 2) or len(select) > 4:
-        raise ValueError("cell_distribution: one or two axes and at most four ranges")
-    d = DistDesc(len(axes), len(select))
-    for k, (coord, lo, width, n) in enumerate(axes):
-        d.axis[k] = DistAxis(CELL_COORDS[coord], int(n), float(lo), float(width))
-    for k, (coord, lo, hi) in enumerate(select):
-        d.sel[k] = DistRange(CELL_COORDS[coord], 0, float(lo), float(hi))
-    return d
-
-
-def cell_dist_values(values):
-    """vpic_hip_dist_value_t[n] of zero to four ((factor, ...), quantum) values, one to three factors each by name: a
-    coordinate of a cell or "one" (KeyError for an unknown one)"""
-    values = list(values)
-    if len(values) > DIST_MAX_VALUES or any(not 1 <= len(f) <= 3 for f, _ in values):
-        raise ValueError("cell_distribution: at most four values of one to three factors each")
-    v = (DistValue * max(len(values), 1))()
-    for k, (factors, quantum) in enumerate(values):
-        codes = [CELL_FACTORS[name] if name in CELL_FACTORS else CELL_COORDS[name] for name in factors]
-        codes += [CELL_FACTORS["one"]] * (3 - len(codes))
-        v[k] = DistValue((C.c_int32 * 3)(*codes), 0, float(quantum))
-    return v, len(values)
-
-
 class SelectDesc(C.Structure):
     """vpic_hip_select_t (include/vpic_hip.h)"""
     _fields_ = [("n_sel", C.c_int32), ("flags", C.c_int32), ("sel", DistRange * 4),
@@ -132,48 +104,63 @@ SELECT_TAG_RANGE, SELECT_TAG_EVERY = 1, 2                                       
 WallTally = collections.namedtuple("WallTally", "count isum_q isum_qke sum_q sum_qke refused")
 WallRecords = collections.namedtuple("WallRecords", "records dropped")
 SelectResult = collections.namedtuple("SelectResult", "count particles fields index")
+PARTICLE_COORDS = dict(DIST_COORDS, **FIELD_COORDS)                 # VPIC_HIP_COORD_* by name
+PARTICLE_FACTORS = dict(PARTICLE_COORDS, **VALUE_FACTORS)            # ("log10_ke" is passed on and refused by the library)
+CELL_FACTOR_CODES = dict(CELL_COORDS, **CELL_FACTORS)
 
 
-def _coord(name):
-    """VPIC_HIP_COORD_* of a coordinate's name (KeyError for an unknown one)"""
-    return FIELD_COORDS[name] if name in FIELD_COORDS else DIST_COORDS[name]
-
-
-def _set_ranges(desc, select):
-    """the (coord, lo, hi) ranges of `select`, coordinates by name, into desc.sel (vpic_hip_dist_range_t[4])"""
+def _set_ranges(desc, select, coords=PARTICLE_COORDS):
+    """the (coord, lo, hi) ranges of `select`, coordinates by name in `coords` (KeyError for an unknown one), into desc.sel
+    (vpic_hip_dist_range_t[4])"""
     for k, (coord, lo, hi) in enumerate(select):
-        desc.sel[k] = DistRange(_coord(coord), 0, float(lo), float(hi))
+        desc.sel[k] = DistRange(coords[coord], 0, float(lo), float(hi))
 
 
-def dist_desc(axes, select=()):
-    """vpic_hip_dist_t of one or two (coord, lo, d, n) axes and up to four (coord, lo, hi) ranges, coordinates by name."""
+def _dist_desc(what, coords, axes, select):
+    """vpic_hip_dist_t of one or two (coord, lo, d, n) axes and up to four (coord, lo, hi) ranges, coordinates by name in
+    `coords` (KeyError for an unknown one)."""
     axes, select = list(axes), list(select)
     if len(axes) not in (1, 2) or len(select) > 4:
-        raise ValueError("distribution: one or two axes and at most four ranges")
+        raise ValueError(what + ": one or two axes and at most four ranges")
     d = DistDesc(len(axes), len(select))
     for k, (coord, lo, width, n) in enumerate(axes):
-        d.axis[k] = DistAxis(_coord(coord), int(n), float(lo), float(width))
-    _set_ranges(d, select)
+        d.axis[k] = DistAxis(coords[coord], int(n), float(lo), float(width))
+    _set_ranges(d, select, coords)
     return d
 
 
-def _factor(name):
-    """VPIC_HIP_FACTOR_* or VPIC_HIP_COORD_* of a factor's name (KeyError for an unknown one; "log10_ke" is passed on and
-    refused by the library)"""
-    return VALUE_FACTORS[name] if name in VALUE_FACTORS else _coord(name)
+def _dist_values(what, least, codes, values):
+    """(vpic_hip_dist_value_t[max(n, 1)], n) of `least` to four ((factor, ...), quantum) values, one to three factors each by name
+    in `codes` (KeyError for an unknown one); codes["one"] fills a value up to three factors"""
+    values = list(values)
+    if not least <= len(values) <= DIST_MAX_VALUES or any(not 1 <= len(f) <= 3 for f, _ in values):
+        raise ValueError(what + " values of one to three factors each")
+    v = (DistValue * max(len(values), 1))()
+    for k, (factors, quantum) in enumerate(values):
+        c = [codes[name] for name in factors]
+        c += [codes["one"]] * (3 - len(c))
+        v[k] = DistValue((C.c_int32 * 3)(*c), 0, float(quantum))
+    return v, len(values)
+
+
+def dist_desc(axes, select=()):
+    """the descriptor of a species distribution: the coordinates of a particle"""
+    return _dist_desc("distribution", PARTICLE_COORDS, axes, select)
+
+
+def cell_dist_desc(axes, select=()):
+    """the descriptor of a cell distribution: the coordinates of a cell ("one" is a factor only)"""
+    return _dist_desc("cell_distribution", CELL_COORDS, axes, select)
 
 
 def dist_values(values):
-    """vpic_hip_dist_value_t[n] of one to four ((factor, ...), quantum) values, one to three factors each by name"""
-    values = list(values)
-    if not 1 <= len(values) <= DIST_MAX_VALUES or any(not 1 <= len(f) <= 3 for f, _ in values):
-        raise ValueError("distribution_sums: one to four values of one to three factors each")
-    v = (DistValue * len(values))()
-    for k, (factors, quantum) in enumerate(values):
-        codes = [_factor(name) for name in factors]
-        codes += [VALUE_FACTORS["one"]] * (3 - len(codes))
-        v[k] = DistValue((C.c_int32 * 3)(*codes), 0, float(quantum))
-    return v
+    """one to four values of a species distribution; a factor is "one", "q", "edotv", "epar_vpar" or a particle coordinate"""
+    return _dist_values("distribution_sums: one to four", 1, PARTICLE_FACTORS, values)[0]
+
+
+def cell_dist_values(values):
+    """(array, n) of zero to four values of a cell distribution; a factor is "one" or a coordinate of a cell"""
+    return _dist_values("cell_distribution: at most four", 0, CELL_FACTOR_CODES, values)
 
 
 def select_desc(select=(), tag_range=None, tag_every=None):
@@ -298,7 +285,7 @@ class Engine:
 
     def emit(self, sp, components, n_emit_per_face, ut_perp, ut_para, coef=32.0 / 81.0, thresh=0.0, seed=1):
         c = np.ascontiguousarray(components, np.int32)
-        self._ck(self._l.vpic_hip_emit(self._h, sp, c.ctypes.data_as(C.c_void_p), len(c), n_emit_per_face, ut_perp, ut_para, coef, thresh, seed))
+        self._ck(self._l.vpic_hip_emit(self._h, sp, _ptr(c), len(c), n_emit_per_face, ut_perp, ut_para, coef, thresh, seed))
 
     def inject_aged(self, inj, tags=None):
         """Appends the injector records inj (particle_injector_t[n], sp_id names the species) and finishes their moves, as
@@ -313,12 +300,12 @@ class Engine:
 
     def set_maxwellian_reflux(self, code, ut_para, ut_perp, seed=1):
         a, b = np.ascontiguousarray(ut_para, np.float32), np.ascontiguousarray(ut_perp, np.float32)
-        self._ck(self._l.vpic_hip_set_maxwellian_reflux(self._h, int(code), a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), len(a), int(seed)))
+        self._ck(self._l.vpic_hip_set_maxwellian_reflux(self._h, int(code), _ptr(a), _ptr(b), len(a), int(seed)))
 
     # ---- absorbing walls that tally and record what they take (include/vpic_hip.h: vpic_hip_wall_*) ----
     def wall_setup(self, q_quantum, qke_quantum, record_cap=0):
         """(Re)allocates and zeroes the tally table and the record buffer; the quanta of the sums of q and of q * ke."""
-        self._ck(self._l.vpic_hip_wall_setup(self._h, float(q_quantum), float(qke_quantum), int(record_cap)))
+        self._ck(self._l.vpic_hip_wall_setup(self._h, q_quantum, qke_quantum, int(record_cap)))
         self._wall_quanta, self._wall_record_cap = (float(q_quantum), float(qke_quantum)), int(record_cap)
 
     def set_wall(self, code, record=False, tally=True):
@@ -334,7 +321,7 @@ class Engine:
         if self._wall_quanta is None:                                # (the sums below need the quanta)
             raise VpicHipError("wall_tally before this Engine's wall_setup")
         t = np.zeros((L.WALL_ROWS, max(n_sp, 1)), L.wall_tally_t)
-        self._ck(self._l.vpic_hip_wall_tally(self._h, _ptr(t), max(n_sp, 1), int(bool(clear))))
+        self._ck(self._l.vpic_hip_wall_tally(self._h, _ptr(t), max(n_sp, 1), bool(clear)))
         t = t[:, :n_sp]
         iq, iqke = t["isum"][..., 0].copy(), t["isum"][..., 1].copy()
         return WallTally(t["count"].copy(), iq, iqke, iq * self._wall_quanta[0], iqke * self._wall_quanta[1], t["refused"].copy())
@@ -346,18 +333,18 @@ class Engine:
         if cap is None:
             cap = self._wall_record_cap
         out = np.zeros(int(cap), L.wall_record_t)
-        self._ck(self._l.vpic_hip_wall_records(self._h, _ptr(out) if cap else None, int(cap), C.byref(n), C.byref(dropped), int(bool(clear))))
+        self._ck(self._l.vpic_hip_wall_records(self._h, _ptr(out) if cap else None, int(cap), C.byref(n), C.byref(dropped), bool(clear)))
         return WallRecords(out[:n.value], int(dropped.value))
 
     def set_reflux_draws(self, draws):
         """Test mode: draws[k] = (uniform, normal, normal) for the particle at index k of its species' array."""
         d = np.ascontiguousarray(draws, np.float32).reshape(-1, 3)
-        self._ck(self._l.vpic_hip_set_reflux_draws(self._h, d.ctypes.data_as(C.c_void_p), len(d)))
+        self._ck(self._l.vpic_hip_set_reflux_draws(self._h, _ptr(d), len(d)))
 
     def set_emit_draws(self, draws):
         """Test mode of emit(): draws[slot] = six numbers, slot = component index * n_emit_per_face + k."""
         d = np.ascontiguousarray(draws, np.float64).reshape(-1, 6)
-        self._ck(self._l.vpic_hip_set_emit_draws(self._h, d.ctypes.data_as(C.c_void_p), len(d)))
+        self._ck(self._l.vpic_hip_set_emit_draws(self._h, _ptr(d), len(d)))
 
     def set_movers(self, sp, pm):
         pm = self._arr(pm, L.particle_mover_t)
@@ -426,7 +413,7 @@ class Engine:
             self._ck(self._l.vpic_hip_set_load_draws(self._h, None, 0))
             return
         d = np.ascontiguousarray(draws, np.float32).reshape(-1, 7)
-        self._ck(self._l.vpic_hip_set_load_draws(self._h, d.ctypes.data_as(C.c_void_p), len(d)))
+        self._ck(self._l.vpic_hip_set_load_draws(self._h, _ptr(d), len(d)))
 
     def np(self, sp):
         return int(self._l.vpic_hip_species_np(self._h, sp))
@@ -474,7 +461,7 @@ class Engine:
 
     def set_accumulation(self, mode, q_ref=0.0):
         """'float' (default) or 'deterministic' (64-bit fixed-point sums: bit-identical from run to run): include/vpic_hip.h."""
-        self._ck(self._l.vpic_hip_set_accumulation(self._h, {"float": 0, "deterministic": 1}[mode], float(q_ref)))
+        self._ck(self._l.vpic_hip_set_accumulation(self._h, {"float": 0, "deterministic": 1}[mode], q_ref))
 
     def advance_p(self, sp):
         """Returns the number of movers, like the reference's advance_p."""
@@ -508,7 +495,7 @@ class Engine:
     def exchange_pack(self, msg_ptrs, caps, mover_cap, species=None):
         """msg_ptrs / caps: per face 0..5, a device pointer (or 0) and the payload capacity of its message;
         species: the species whose movers are packed (default: all)."""
-        m = (C.c_void_p * 6)(*[C.c_void_p(p or None) for p in msg_ptrs])
+        m = (C.c_void_p * 6)(*[p or None for p in msg_ptrs])
         c = (C.c_int32 * 6)(*[int(x) for x in caps])
         if species is None:
             self._ck(self._l.vpic_hip_exchange_pack(self._h, m, c, int(mover_cap)))
@@ -517,13 +504,13 @@ class Engine:
             self._ck(self._l.vpic_hip_exchange_pack_species(self._h, mask, m, c, int(mover_cap)))
 
     def exchange_inject(self, msg_ptr, cap):
-        self._ck(self._l.vpic_hip_exchange_inject(self._h, C.c_void_p(msg_ptr), int(cap)))
+        self._ck(self._l.vpic_hip_exchange_inject(self._h, msg_ptr, int(cap)))
 
     def exchange_finish(self, recv_ptrs):
         """The one synchronisation of the particle exchange.  Returns the headers of the received messages
         ([count, wanted, 0, 0] each); np / nm of every species are current on the host afterwards."""
         n = len(recv_ptrs)
-        r = (C.c_void_p * max(n, 1))(*[C.c_void_p(p) for p in recv_ptrs])
+        r = (C.c_void_p * max(n, 1))(*recv_ptrs)
         h = (C.c_int32 * (4 * max(n, 1)))()
         flags = C.c_int32()
         self._ck(self._l.vpic_hip_exchange_finish(self._h, r, n, h, C.byref(flags)))
@@ -534,7 +521,7 @@ class Engine:
         self._ck(self._l.vpic_hip_advance_e_part(self._h, int(part)))
 
     def stream_wait_event(self, hip_event):
-        self._ck(self._l.vpic_hip_stream_wait_event(self._h, C.c_void_p(hip_event)))
+        self._ck(self._l.vpic_hip_stream_wait_event(self._h, hip_event))
 
     def sort_p(self, sp):
         self._ck(self._l.vpic_hip_sort_p(self._h, sp))
@@ -587,7 +574,7 @@ class Engine:
             self._ck(self._l.vpic_hip_set_collide_draws(self._h, None, 0))
             return
         d = np.ascontiguousarray(draws, np.float32).reshape(-1, 4)
-        self._ck(self._l.vpic_hip_set_collide_draws(self._h, d.ctypes.data_as(C.c_void_p), len(d)))
+        self._ck(self._l.vpic_hip_set_collide_draws(self._h, _ptr(d), len(d)))
 
     # ---- energy spectra (include/vpic_hip.h: vpic_hip_energy_spectrum) ----
     def energy_spectrum(self, sp, n_lin=0, d_lin=0.0, n_log=0, log_lo=0.0, d_log=0.0):
@@ -766,11 +753,11 @@ class Engine:
     def set_hydro(self, h):
         h = np.ascontiguousarray(h, L.hydro_t)
         assert len(h) == self.nv
-        self._ck(self._l.vpic_hip_set_hydro(self._h, h.ctypes.data_as(C.c_void_p)))
+        self._ck(self._l.vpic_hip_set_hydro(self._h, _ptr(h)))
 
     def get_hydro(self):
         h = np.zeros(self.nv, L.hydro_t)
-        self._ck(self._l.vpic_hip_get_hydro(self._h, h.ctypes.data_as(C.c_void_p)))
+        self._ck(self._l.vpic_hip_get_hydro(self._h, _ptr(h)))
         return h
 
     def dump_gather(self, what, layout, words=(), strides=(1, 1, 1)):
@@ -783,8 +770,8 @@ class Engine:
         shape = (len(words), dim[2], dim[1], dim[0]) if layout == 0 else (dim[2], dim[1], dim[0], W)
         out = np.zeros(shape, np.uint32)
         w = np.asarray(words, np.int32)
-        self._ck(self._l.vpic_hip_dump_gather(self._h, what, layout, w.ctypes.data_as(C.c_void_p), len(w), int(strides[0]),
-                                              int(strides[1]), int(strides[2]), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes)))
+        self._ck(self._l.vpic_hip_dump_gather(self._h, what, layout, _ptr(w), len(w), int(strides[0]),
+                                              int(strides[1]), int(strides[2]), _ptr(out), out.nbytes))
         return out
 
     # ---- divergence cleaning family and charge densities (field_advance.h:242-302, spa.h:108-113) ----
@@ -866,25 +853,25 @@ class Engine:
         return self._l.vpic_hip_boundary_p_send_buffer(self._h, face)
 
     def get_injectors(self, face, dev_ptr):
-        self._ck(self._l.vpic_hip_boundary_p_get_injectors(self._h, face, C.c_void_p(dev_ptr)))
+        self._ck(self._l.vpic_hip_boundary_p_get_injectors(self._h, face, dev_ptr))
 
     def boundary_p_inject(self, dev_ptr, n):
-        self._ck(self._l.vpic_hip_boundary_p_inject(self._h, C.c_void_p(dev_ptr), int(n)))
+        self._ck(self._l.vpic_hip_boundary_p_inject(self._h, dev_ptr, int(n)))
 
     def face_count(self, d):
         return self._l.vpic_hip_face_count(self._h, d)
 
     def pack_tang_b(self, d, dev_ptr):
-        self._ck(self._l.vpic_hip_pack_tang_b(self._h, d, C.c_void_p(dev_ptr)))
+        self._ck(self._l.vpic_hip_pack_tang_b(self._h, d, dev_ptr))
 
     def unpack_tang_b(self, d, dev_ptr):
-        self._ck(self._l.vpic_hip_unpack_tang_b(self._h, d, C.c_void_p(dev_ptr)))
+        self._ck(self._l.vpic_hip_unpack_tang_b(self._h, d, dev_ptr))
 
     def pack_jf(self, d, dev_ptr):
-        self._ck(self._l.vpic_hip_pack_jf(self._h, d, C.c_void_p(dev_ptr)))
+        self._ck(self._l.vpic_hip_pack_jf(self._h, d, dev_ptr))
 
     def unpack_jf(self, d, dev_ptr):
-        self._ck(self._l.vpic_hip_unpack_jf(self._h, d, C.c_void_p(dev_ptr)))
+        self._ck(self._l.vpic_hip_unpack_jf(self._h, d, dev_ptr))
 
     # pieces of the divergence-cleaning family for domains that share faces with other domains
     def local_adjust_rho(self):
@@ -897,10 +884,10 @@ class Engine:
         return self._l.vpic_hip_rho_count(self._h, d)
 
     def pack_rho(self, d, dev_ptr):
-        self._ck(self._l.vpic_hip_pack_rho(self._h, d, C.c_void_p(dev_ptr)))
+        self._ck(self._l.vpic_hip_pack_rho(self._h, d, dev_ptr))
 
     def unpack_rho(self, d, dev_ptr):
-        self._ck(self._l.vpic_hip_unpack_rho(self._h, d, C.c_void_p(dev_ptr)))
+        self._ck(self._l.vpic_hip_unpack_rho(self._h, d, dev_ptr))
 
     # ... and of the hydro moments (sf_interface/hydro.c:28-200)
     def local_adjust_hydro(self):
@@ -913,21 +900,21 @@ class Engine:
         return self._l.vpic_hip_hydro_count(self._h, d)
 
     def pack_hydro(self, d, dev_ptr):
-        self._ck(self._l.vpic_hip_pack_hydro(self._h, d, C.c_void_p(dev_ptr)))
+        self._ck(self._l.vpic_hip_pack_hydro(self._h, d, dev_ptr))
 
     def unpack_hydro(self, d, dev_ptr):
-        self._ck(self._l.vpic_hip_unpack_hydro(self._h, d, C.c_void_p(dev_ptr)))
+        self._ck(self._l.vpic_hip_unpack_hydro(self._h, d, dev_ptr))
 
     def message_count(self, kind, d):
         return self._l.vpic_hip_face_message_count(self._h, kind, d)
 
     def pack_message(self, kind, d, dev_ptr):
-        self._ck(self._l.vpic_hip_pack_face_message(self._h, kind, d, C.c_void_p(dev_ptr)))
+        self._ck(self._l.vpic_hip_pack_face_message(self._h, kind, d, dev_ptr))
 
     def unpack_message(self, kind, d, dev_ptr):
         """Returns the squared-difference sum of a kind-2 message, 0.0 otherwise."""
         err = C.c_double()
-        self._ck(self._l.vpic_hip_unpack_face_message(self._h, kind, d, C.c_void_p(dev_ptr), C.byref(err)))
+        self._ck(self._l.vpic_hip_unpack_face_message(self._h, kind, d, dev_ptr, C.byref(err)))
         return err.value
 
     def local_adjust_tang_e_norm_b(self):

@@ -388,10 +388,9 @@ def test_distribution_of_the_draws():
 def set_momenta(e, sp, p):
     """the library's test hook: ux, uy, uz of the array as it lies, nothing else (the order and the partition stay)"""
     import ctypes as C
-    f = package().lib().vpic_hip_debug_set_momenta
-    f.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int64]
+    f = package().lib().vpic_hip_debug_set_momenta              # (a test hook that no header declares: the arguments say their types)
     u = [np.ascontiguousarray(p[c], F) for c in ("ux", "uy", "uz")]
-    assert f(e._h, sp, *[x.ctypes.data_as(C.c_void_p) for x in u], len(p)) == 0
+    assert f(e._h, C.c_int(sp), *[x.ctypes.data_as(C.c_void_p) for x in u], C.c_int64(len(p))) == 0
 
 
 def test_seeds():

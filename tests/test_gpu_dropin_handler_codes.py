@@ -33,9 +33,7 @@ def world(code):
     _, _, og = D.grids(DIMS, [L.ABSORB_PARTICLES, 0, 0, L.ABSORB_PARTICLES, 0, 0])
     fi = D.interpolator(og)
     p = D.particles(61, 3000, DIMS, 0.5)
-    l = drop.ref()
-    l.vpic_hip_ref_center_p.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
-    return l, g, fi, p
+    return drop.ref(), g, fi, p
 
 
 def test_center_p_and_energy_p_do_not_look_at_the_code():

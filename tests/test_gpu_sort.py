@@ -88,10 +88,9 @@ def upload(V, e, sp, p, any_voxel=False):
     if not any_voxel:
         e.set_particles(sp, p)
         return
-    f = V.lib().vpic_hip_debug_set_particles_any_voxel
-    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]
+    f = V.lib().vpic_hip_debug_set_particles_any_voxel          # (a test hook that no header declares: the arguments say their types)
     p = np.ascontiguousarray(p, V.layout.particle_t)
-    if f(e._h, sp, p.ctypes.data_as(C.c_void_p), len(p)):
+    if f(e._h, C.c_int(sp), p.ctypes.data_as(C.c_void_p), C.c_int64(len(p))):
         raise V.VpicHipError(V.lib().vpic_hip_last_error().decode())
 
 
