@@ -574,6 +574,58 @@ int vpic_hip_set_collide_draws(vpic_hip_engine_t *e, const float *draws, int64_t
  * ln(Lambda) as before). */
 int vpic_hip_collide_relativistic(vpic_hip_engine_t *e, const vpic_hip_collision_t *c);
 
+/* ---- radiative cooling of one species: synchrotron losses and Compton drag (csrc/cool.hip) ----
+ * Another stage for a deck's user_particle_collisions (between the sort and the push): one pass over a species that changes
+ * ux, uy, uz and nothing else.  The model is the leading terms of the Landau-Lifshitz radiation-reaction force, in the form
+ * radiative PIC codes use, plus the Thomson drag of an isotropic photon bath.  u is the momentum per mass in units of c, v =
+ * u / gamma; E and cB are as the field array holds them.  The caller folds every unit into two numbers:
+ *   sync = tau0 (q / m c)^2 times the time the call stands for, tau0 = q^2 / (6 pi eps0 m c^3) of a PHYSICAL particle; then
+ *          du = sync { (E + v x cB) x cB + (v.E) E - gamma^2 [ (E + v x cB)^2 - (v.E)^2 ] v }
+ *   ic   = (4/3) sigma_T U_ph / (m c) times that time (U_ph the energy density of the photons): du = -ic gamma u
+ * THE RULE, a contract (tests/cool_ref.py restates it in numpy; tests/test_gpu_cool.py holds every word to it).
+ *   Per live particle: 0 <= i < nv; dead slots (i = -1) are skipped, particles appended since the last sort are included, a
+ *   particle in a ghost voxel uses that voxel's record.  ex .. cbz are the float fields at the particle exactly as
+ *   vpic_hip_species_select below states them, from the interpolator AS IT IS LOADED at the call, then promoted to double
+ *   Ex .. Bz; ux, uy, uz are promoted.  Everything after that is IEEE double, every operation rounded once, unfused, / and
+ *   sqrt correctly rounded, the parentheses as written:
+ *     u2 = (ux*ux + uy*uy) + uz*uz;   g = sqrt(1 + u2);   rg = 1 / g;   vx = ux*rg;  vy = uy*rg;  vz = uz*rg
+ *     Lx = Ex + (vy*Bz - vz*By);   Ly = Ey + (vz*Bx - vx*Bz);   Lz = Ez + (vx*By - vy*Bx)
+ *     vE = (vx*Ex + vy*Ey) + vz*Ez
+ *     Ax = (Ly*Bz - Lz*By) + vE*Ex;   Ay = (Lz*Bx - Lx*Bz) + vE*Ey;   Az = (Lx*By - Ly*Bx) + vE*Ez
+ *     L2 = (Lx*Lx + Ly*Ly) + Lz*Lz;   chi = L2 - vE*vE;   chi < 0: chi = 0   (a NaN stays a NaN)
+ *     D  = g * (sync*chi + ic);   den = 1 + D              (gamma^2 v = gamma u: the drag term is -D u, taken implicitly)
+ *     nx = (ux + sync*Ax) / den;  ny, nz likewise;   ux' = (float)nx,  uy', uz' likewise   (one rounding each)
+ *     D, nx, ny or nz not finite: the particle is LEFT ALONE -- nothing written, nothing tallied, counted in out[3]
+ *     u2n = (ux'*ux' + uy'*uy') + uz'*uz' of the promoted new floats;   g1 = sqrt(1 + u2n)
+ *     val = (double)fabsf(q) * ((u2 - u2n) / (g + g1))     (|q| (gamma - gamma'), without the cancellation)
+ *     t = val / quantum;  fabs(t) < 2^32: the particle adds llrint(t) (to nearest, ties to even) to *energy and, when
+ *     cell_energy is given, to cell_energy[i]; otherwise (a NaN included) it adds nothing and is counted in out[2] -- its
+ *     momenta are still written
+ * *energy is the energy the drag took from the species, in units of quantum: a signed sum of integers (with E present the
+ * retained terms can give a slow particle energy), so it is bit-identical in every array order and launch shape and adds
+ * exactly across ranks.  sum |q| (gamma - 1) before the call minus the same after equals *energy * quantum to half a quantum
+ * per particle.  cell_energy (nv words in host memory, or NULL) is the same per voxel: the map of the emitted power.  With
+ * VPIC_HIP_COOL_DRY the same tallies are returned and no byte of the species changes.
+ * Range of validity.  The drag term is implicit: D may be anything, and |u'| -> 0 as D -> inf.  The A term is explicit: the
+ * operator is meant for sync (|E| + |cB|)^2 << 1, which every physical setting satisfies by many orders; above that a slow
+ * particle overshoots.  First order in the time the call stands for, and an operator split from the push: the stored momenta
+ * are half a step behind the fields, as they are for the collisions.  No quantum corrections, no photons.
+ * What the call touches: ux, uy, uz of sp and nothing else.  No cell changes, so positions, voxels, q, tags, the order of the
+ * array, partition[] / tpart[], the push's pending histogram and a sort pending inside the next push all stay valid; host
+ * mirrors go stale as after a push.
+ * Fails (non-zero, vpic_hip_last_error names the argument, nothing is touched -- the species, the last statistics and the
+ * caller's arrays) on a bad sp, a NULL c or energy, sync or ic negative or not finite, quantum not positive and finite, unknown
+ * flag bits, or a device allocation that fails (the scratch belongs to the engine and grows on demand: 8 bytes per voxel).
+ * "Nothing is touched" holds for these two kinds of failure, which come before the launch; a runtime error behind them (a
+ * launch or a copy that fails) also returns non-zero and leaves the last statistics alone, but momenta may have been written. */
+enum { VPIC_HIP_COOL_DRY = 1 };              /* tally only: no momentum is written */
+typedef struct { double sync, ic, quantum; int32_t flags, pad; } vpic_hip_cool_t;
+VPIC_HIP_STATIC_ASSERT(sizeof(vpic_hip_cool_t) == 32, "vpic_hip_cool_t layout");
+int vpic_hip_species_cool(vpic_hip_engine_t *e, int sp, const vpic_hip_cool_t *c, int64_t *energy, int64_t *cell_energy);
+/* The last call: out[0] live particles seen, out[1] particles whose three new floats differ from the stored ones in any bit
+ * (in a dry run: those that would), out[2] particles refused for the tally, out[3] particles left alone. */
+int vpic_hip_species_cool_stats(vpic_hip_engine_t *e, int64_t out[4]);
+
 /* ---- energy spectra of a species (the diagnostic of decks/trecon-part/energy.cxx, computed where the particles are) ----
  * One pass over the species' stored momenta (no half-step field correction, unlike energy_p).  Per live particle
  * (dead slots are skipped, particles appended since the last sort are included), energy.cxx:96-108 restated:

@@ -89,6 +89,18 @@ __device__ __forceinline__ DistField dist_gather(const vpic_interpolator_t *__re
 }
 static_assert(sizeof(vpic_interpolator_t) == 80, "an interpolator record is five float4");
 
+// THE FIELDS AT THE PARTICLE as select_write_kernel forms them (advance_p.cxx:74-82 without qdt_2mc: float, every operation
+// rounded once, unfused), of a gathered record: the one statement behind the field coordinates, the factors and cool.hip
+// (select_write_kernel keeps its own, over the words it loads itself)
+__device__ __forceinline__ float3 dist_b_at(const DistRaw &r, const DistField &f) {
+  return make_float3(f.b.x + r.dx * f.b.y, f.b.z + r.dy * f.b.w, f.c.x + r.dz * f.c.y);
+}
+__device__ __forceinline__ float3 dist_e_at(const DistRaw &r, const DistField &f) {
+  return make_float3((f.ex.x + r.dy * f.ex.y) + r.dz * (f.ex.z + r.dy * f.ex.w),
+                     (f.ey.x + r.dz * f.ey.y) + r.dx * (f.ey.z + r.dz * f.ey.w),
+                     (f.ez.x + r.dx * f.ez.y) + r.dy * (f.ez.z + r.dx * f.ez.w));
+}
+
 // The coordinates that `need` names of a LIVE particle (0 <= r.voxel < nv); cx, cy, cz: the decoded voxel, ghost layer
 // included (set when a position is needed, otherwise left alone).  f: its voxel's record (FIELDS instances only).
 template <bool FIELDS>
@@ -109,7 +121,8 @@ __device__ __forceinline__ DistCoords dist_coords(const DistRaw &r, const DistFi
   if (FIELDS) {
     // the fields at the particle as select_write_kernel forms them (float, unfused), then double, summed from the left;
     // no special case: B == 0 and u == 0 give what the quotients give
-    const double bx = (double)(f.b.x + r.dx * f.b.y), by = (double)(f.b.z + r.dy * f.b.w), bz = (double)(f.c.x + r.dz * f.c.y);
+    const float3 cb = dist_b_at(r, f);
+    const double bx = (double)cb.x, by = (double)cb.y, bz = (double)cb.z;
     const double b = sqrt((bx * bx + by * by) + bz * bz);
     v.b = b;
     if (need & NEED_FIELD_U) {
@@ -125,10 +138,8 @@ __device__ __forceinline__ DistCoords dist_coords(const DistRaw &r, const DistFi
       if (need & 1u << VPIC_HIP_COORD_PITCH) v.pitch = u_par / sqrt(u2);
     }
     if (need & NEED_FIELD_E) {
-      const float ex = (f.ex.x + r.dy * f.ex.y) + r.dz * (f.ex.z + r.dy * f.ex.w);
-      const float ey = (f.ey.x + r.dz * f.ey.y) + r.dx * (f.ey.z + r.dz * f.ey.w);
-      const float ez = (f.ez.x + r.dx * f.ez.y) + r.dy * (f.ez.z + r.dx * f.ez.w);
-      v.e_par = (((double)ex * bx + (double)ey * by) + (double)ez * bz) / b;
+      const float3 el = dist_e_at(r, f);
+      v.e_par = (((double)el.x * bx + (double)el.y * by) + (double)el.z * bz) / b;
     }
   }
   return v;
@@ -155,7 +166,7 @@ __device__ __forceinline__ float dist_load_q(const ParticlesK &p, long long idx,
 }
 
 // Of a LIVE particle whose coordinates v dist_coords has formed under dist_factor_need's bits.  E at the particle is
-// formed again by the expressions of dist_coords (the same float operations give the same floats).
+// formed again by dist_e_at (the same float operations give the same floats).
 template <bool FIELDS>
 __device__ __forceinline__ DistExtra dist_extra(const DistRaw &r, const DistField &f, float q, const DistCoords &v, unsigned vneed) {
   DistExtra x{};
@@ -163,10 +174,8 @@ __device__ __forceinline__ DistExtra dist_extra(const DistRaw &r, const DistFiel
   if (FIELDS && (vneed & (VAL_EDOTV | VAL_EPAR_VPAR))) {
     const double gamma = sqrt(((1.0 + v.ux * v.ux) + v.uy * v.uy) + v.uz * v.uz);   // KE's expression before the - 1
     if (vneed & VAL_EDOTV) {
-      const float ex = (f.ex.x + r.dy * f.ex.y) + r.dz * (f.ex.z + r.dy * f.ex.w);
-      const float ey = (f.ey.x + r.dz * f.ey.y) + r.dx * (f.ey.z + r.dz * f.ey.w);
-      const float ez = (f.ez.x + r.dx * f.ez.y) + r.dy * (f.ez.z + r.dx * f.ez.w);
-      x.edotv = (((double)ex * v.ux + (double)ey * v.uy) + (double)ez * v.uz) / gamma;
+      const float3 el = dist_e_at(r, f);
+      x.edotv = (((double)el.x * v.ux + (double)el.y * v.uy) + (double)el.z * v.uz) / gamma;
     }
     if (vneed & VAL_EPAR_VPAR) x.epar_vpar = (v.e_par * v.u_par) / gamma;
   }

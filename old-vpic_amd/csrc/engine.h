@@ -447,6 +447,10 @@ struct Engine {
   float *collide_draws = nullptr; int64_t collide_draws_n = 0;
   unsigned long long *collide_dev = nullptr, *collide_host = nullptr;
   int64_t collide_last[6] = {0, 0, 0, 0, 0, 0}; int collide_instance = 0;
+  // radiative cooling (cool.hip), allocated by the first call that asks for them and grown on demand: the per-voxel sums
+  // and the pinned words they come back through; statistics {seen, changed, refused, left alone, the species' sum}
+  unsigned long long *cool_cells = nullptr, *cool_cells_host = nullptr; size_t cool_cells_n = 0;
+  DiagStats<8> cool_stats;
   // species loaded from per-cell tables (load.hip), allocated by the first call and grown on demand: the parity mode's draws
   // (7 floats per particle place) and the call's tables as uploaded
   float *load_draws = nullptr; int64_t load_draws_n = 0;
@@ -541,6 +545,8 @@ int k_species_select(Engine *e, Species &s, const vpic_hip_select_t &d, int64_t 
 // collide.hip: the checking pass, the sorts it asks for, the launch; wants_tile_a / _b: the order a sort of that species would produce now;
 // relativistic: the pair of vpic_hip_collide_relativistic
 int k_collide(Engine *e, const vpic_hip_collision_t &c, bool wants_tile_a, bool wants_tile_b, bool relativistic);
+// cool.hip: one pass over the species (a checked descriptor); the sums into Engine::cool_stats and, with cells, cool_cells_host; waits for the stream
+int k_species_cool(Engine *e, Species &s, const vpic_hip_cool_t &c, bool cells);
 int k_sort_p(Engine *e, Species &s, bool tile_order = false, bool may_fuse = false);   // may_fuse: the caller pushes the species next (see Species::fuse_pending)
 int k_sort_scan(Engine *e, const int *counts, int *starts, int n1);                  // exclusive scan of counts[0..n1) into starts[] and Engine::sort_next[]
 int k_sort_check(Engine *e, Species &s, const int *starts, int n1);                    // every cursor ended where the next key begins? (PW_SORT_CHECK; the next push fails loudly otherwise)

@@ -196,6 +196,7 @@ static void destroy(Engine *e) {
   (void)hipFree(e->wall_table); (void)hipFree(e->wall_rec); (void)hipFree(e->wall_cursor);
   (void)hipFree(e->collide_draws); (void)hipFree(e->collide_dev); (void)hipHostFree(e->collide_host);
   (void)hipFree(e->load_draws); (void)hipFree(e->load_tab);
+  (void)hipFree(e->cool_cells); (void)hipHostFree(e->cool_cells_host); e->cool_stats.release();
   (void)hipFree(e->hole_list); (void)hipFree(e->fill_list); (void)hipFree(e->tail_flag);
   (void)hipFree(e->sp_table_dev); (void)hipHostFree(e->sp_table_host); (void)hipFree(e->xmsg_dev); (void)hipHostFree(e->xmsg_host);
   (void)hipFree(e->retry_buf); (void)hipFree(e->tile_list[0]); (void)hipFree(e->tile_list[1]);
@@ -981,6 +982,23 @@ int vpic_hip_species_select(vpic_hip_engine_t *e, int sp, const vpic_hip_select_
   return 0;
 }
 int vpic_hip_species_select_stats(vpic_hip_engine_t *e, int64_t out[4]) { ENGINE(e); return copy_stats(e->sel_stats.last, out, 4); }
+// Radiative cooling (cool.hip).  The arguments are checked here, before anything is touched; the message names the argument.
+int vpic_hip_species_cool(vpic_hip_engine_t *e, int sp, const vpic_hip_cool_t *c, int64_t *energy, int64_t *cell_energy) {
+  ENGINE(e);
+  if (sp < 0 || (size_t)sp >= e->species.size()) VH_FAIL("cool: sp = %d is not a species", sp);
+  if (!c) VH_FAIL("cool: NULL c");
+  if (!energy) VH_FAIL("cool: NULL energy");
+  if (!(c->sync >= 0) || !std::isfinite(c->sync)) VH_FAIL("cool: sync = %g must be finite and not negative", c->sync);
+  if (!(c->ic >= 0) || !std::isfinite(c->ic)) VH_FAIL("cool: ic = %g must be finite and not negative", c->ic);
+  if (!(c->quantum > 0) || !std::isfinite(c->quantum)) VH_FAIL("cool: quantum = %g must be finite and above 0", c->quantum);
+  if (c->flags & ~VPIC_HIP_COOL_DRY) VH_FAIL("cool: unknown flag bits 0x%x", (unsigned)c->flags);
+  const size_t cell_bytes = sizeof(int64_t) * (size_t)e->gk.nv;
+  if (k_species_cool(e, e->species[sp], *c, cell_energy != nullptr)) return 1;
+  *energy = e->cool_stats.last[4];
+  if (cell_energy) { host_will_write(cell_energy, cell_bytes); memcpy(cell_energy, e->cool_cells_host, cell_bytes); }
+  return 0;
+}
+int vpic_hip_species_cool_stats(vpic_hip_engine_t *e, int64_t out[4]) { ENGINE(e); return copy_stats(e->cool_stats.last, out, 4); }
 int vpic_hip_center_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp); return k_center_p(e, e->species[sp], false); }
 int vpic_hip_uncenter_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp); return k_center_p(e, e->species[sp], true); }
 int vpic_hip_clear_jf(vpic_hip_engine_t *e) { ENGINE(e); return k_clear_jf(e); }

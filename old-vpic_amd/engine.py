@@ -14,6 +14,7 @@ import numpy as np
 
 from . import layout as L
 from ._lib import lib
+from .cool import COOL_DRY, CoolDesc, CoolResult  # noqa: F401
 
 
 class VpicHipError(RuntimeError):
@@ -575,6 +576,29 @@ class Engine:
             return
         d = np.ascontiguousarray(draws, np.float32).reshape(-1, 4)
         self._ck(self._l.vpic_hip_set_collide_draws(self._h, _ptr(d), len(d)))
+
+    # ---- radiative cooling (include/vpic_hip.h: vpic_hip_species_cool) ----
+    def cool(self, sp, sync, ic=0.0, quantum=2.0 ** -40, dry=False, cells=False):
+        """Synchrotron losses and Compton drag of one species on the device, one pass that changes ux, uy, uz and nothing
+        else: sync = tau0 (q / m c)^2 and ic = (4/3) sigma_T U_ph / (m c), each times the time the call stands for (the
+        header states the rule operation by operation).  The fields are those of the interpolator as it is loaded at the
+        call.  Returns CoolResult(isum, energy, cell_isums, stats): isum the energy the drag took, sum |q| (gamma - gamma'),
+        as an exact integer sum in units of quantum (the same in every array order), energy = isum * quantum, cell_isums
+        int64[nv] the same per voxel (cells=True) or None, stats a dict of seen, changed, refused (for the tally: |val /
+        quantum| >= 2^32) and left_alone (a result that is not finite).  dry=True returns the same tallies and writes
+        nothing.  A copy of the species' particles held on the host is stale afterwards."""
+        d = CoolDesc(float(sync), float(ic), float(quantum), COOL_DRY if dry else 0, 0)
+        isum = C.c_int64()
+        cell = np.zeros(self.nv, np.int64) if cells else None
+        self._ck(self._l.vpic_hip_species_cool(self._h, int(sp), C.byref(d), C.byref(isum), _ptr(cell) if cells else None))
+        return CoolResult(isum.value, isum.value * float(quantum), cell, self.cool_stats())
+
+    def cool_stats(self):
+        """dict of the last cool call: live particles seen, particles whose momenta changed in any bit (dry: would have),
+        particles refused for the tally, particles left alone."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._l.vpic_hip_species_cool_stats(self._h, out))
+        return dict(zip(("seen", "changed", "refused", "left_alone"), [int(v) for v in out]))
 
     # ---- energy spectra (include/vpic_hip.h: vpic_hip_energy_spectrum) ----
     def energy_spectrum(self, sp, n_lin=0, d_lin=0.0, n_log=0, log_lo=0.0, d_log=0.0):

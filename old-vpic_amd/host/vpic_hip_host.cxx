@@ -622,6 +622,23 @@ void vpic_simulation::collide(species_t *a, species_t *b, const collide_params_t
   if ((size_t)ib < sort_pending.size()) sort_pending[(size_t)ib] = 0;
   mirrors_stale();
 }
+double vpic_simulation::cool(species_t *sp, const cool_params_t &prm, int64_t *cell_energy) {
+  if (!sp) ERROR(("Invalid species"));
+  const int id = resident_id(sp->p);
+  if (!engine || id < 0) ERROR(("cool before the run has started is not supported by this host"));
+  if (prm.interval < 1) ERROR(("cool: interval %d", prm.interval));
+  if (step % prm.interval) return 0;
+  mirrors_after_user_code();                              // what the hook wrote so far goes to the device; the mirrors are stale from here
+  const double t = (double)prm.interval * (double)grid->dt;
+  vpic_hip_cool_t c;
+  memset(&c, 0, sizeof(c));
+  c.sync = prm.sync_rate * t; c.ic = prm.ic_rate * t; c.quantum = prm.quantum;
+  c.flags = prm.dry ? VPIC_HIP_COOL_DRY : 0;
+  int64_t isum = 0;
+  CK(vpic_hip_species_cool(engine, id, &c, &isum, cell_energy));
+  mirrors_stale();
+  return (double)isum * prm.quantum;
+}
 // a deck's histogram for the engine: position axes and ranges from physical units to cells of this domain; x_code: the
 // code of X, with Y and Z behind it (a particle's VPIC_HIP_COORD_X, or a cell's VPIC_HIP_CELL_X)
 static vpic_hip_dist_t distribution_in_cells(const vpic_hip_dist_t &d, const grid_t *grid, int x_code = VPIC_HIP_COORD_X) {

@@ -404,6 +404,23 @@ public:
     int relativistic;         // 0: vpic_hip_collide (|u| << 1); non-zero: vpic_hip_collide_relativistic (hot plasmas; include/vpic_hip.h gives the range of |u|).  An initialiser of seven values leaves it 0
   };
   void collide(species_t *a, species_t *b, const collide_params_t &prm);
+  // Radiative cooling of a species on the device: synchrotron losses and the Compton drag of an isotropic photon bath
+  // (vpic_hip_species_cool, include/vpic_hip.h: the model, the arithmetic, its range of validity), in place of a hook that
+  // walks sp->p and the interpolator on the host.  For begin_particle_collisions: the call does its work on the steps that
+  // are multiples of prm.interval, for the time interval * grid->dt, and returns at once with 0 on the others.  Returns the
+  // energy the drag took from the species, sum |q| (gamma - gamma'), as isum * quantum: an exact integer sum, so the
+  // returns of the ranks add exactly; cell_energy (grid->nv words, or NULL) takes the same per voxel in units of quantum.
+  // With dry the tallies are returned and no momentum is written.  What a hook has written to sp->p or to the interpolator
+  // before the call reaches the device first; afterwards the particle mirrors are stale like after a push, and none is
+  // brought to the host.  Running totals are the deck's business: its globals travel in the restart file.
+  struct cool_params_t {
+    double sync_rate;         // tau0 (q / m c)^2 per unit time, tau0 = q^2 / (6 pi eps0 m c^3) of a physical particle
+    double ic_rate;           // (4/3) sigma_T U_ph / (m c) per unit time
+    int interval;             // cool every `interval` steps, for the time interval * dt
+    double quantum;           // the unit of the integer sums
+    int dry;                  // non-zero: tally only
+  };
+  double cool(species_t *sp, const cool_params_t &prm, int64_t *cell_energy = NULL);
   int64_t particle_mirror_downloads(void) const;    // whole-species downloads into the host mirrors so far (diagnostics, tests)
   int64_t particle_mirror_uploads(void) const;      // particles that went from a host mirror to the device so far
   // A species loaded on the device from per-cell tables (vpic_hip_species_load_profile, include/vpic_hip.h: THE RULE, the
