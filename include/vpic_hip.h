@@ -269,7 +269,8 @@ int vpic_hip_species_get_particles_range(vpic_hip_engine_t *e, int sp, vpic_part
 int vpic_hip_push_plan(int64_t np, int iters, int64_t *start, int32_t *count, uint32_t *grid, int max_segments);
 /* Synthetic loader for benchmark-sized species: ppc particles in every interior cell, uniform in
  * the cell, drifting Maxwellian momenta -- what a deck's `repeat(N) inject_particle(...)` loop does
- * (src/vpic/vpic.hxx:491-505), on the device with a counter-based generator. */
+ * (src/vpic/vpic.hxx:491-505), on the device with a counter-based generator.  The loaded particles carry tag = tag2 = 0,
+ * whatever tags the species held before. */
 int vpic_hip_species_load_maxwellian(vpic_hip_engine_t *e, int sp, int ppc, uint32_t seed, float q,
                                      float ux, float uy, float uz, float vth);
 /* A species loaded on the device from per-cell tables, the same particles for any decomposition of the global grid.
@@ -426,6 +427,11 @@ int vpic_hip_set_push_mode(vpic_hip_engine_t *e, int mode);
  * range (vpic_hip_moments_stats: out[3]).  Float mode has no such limit. */
 int vpic_hip_set_accumulation(vpic_hip_engine_t *e, int mode, double q_ref);
 int vpic_hip_advance_p(vpic_hip_engine_t *e, int sp);       /* species_advance/standard/advance_p.cxx:399-472 (+move_p.c); movers: vpic_hip_species_nm */
+/* A mover names its particle by array index, so no call reorders a species while movers of it are pending (_species_nm > 0, or
+ * between the two phases of its push): vpic_hip_sort_p -- and every call that would have to sort, such as _species_get_particles
+ * of a species with dead slots -- fails and leaves the species, its movers and its books as they were, the ordering
+ * _exchange_begin does before a deterministic push passes such a species by, and a call that pushes (_advance_p,
+ * _sort_advance_p, _step) begins a new mover list, so it drops what is left of the old one before it orders the species. */
 int vpic_hip_sort_p(vpic_hip_engine_t *e, int sp);
 /* sort_p followed by advance_p of the same species, as ONE call: when the sort is by tile and cell and finds the counts the
  * push before it took (vpic_hip_species_sort_hint), the push writes every particle straight to its sorted place in the

@@ -676,6 +676,8 @@ static float event_ms(const hipEvent_t ev[2], bool wait = false) {
   return ms;
 }
 static int order_for_deterministic_push(Engine *e, Species &s) {
+  // (movers pending: a recovery round's second _exchange_begin; the first one of the step ordered the species if it could be)
+  if (s.nm > 0 || s.phase_pending) return 0;
   if (e->det_acc && !s.chargeless && !s.tile_valid && s.np > 0 && wants_tile_order(e, s)) return k_sort_p(e, s, true);
   return 0;
 }
@@ -694,7 +696,13 @@ static int push_timing_hinted(Engine *e, Species &s) {
   if (timed) { VH_CHECK(hipEventRecord(s.hp_ev[1], e->stream)); s.hp_pending = true; }
   return 0;
 }
-int vpic_hip_advance_p(vpic_hip_engine_t *e, int sp) { ENGINE(e); SPECIES(e, sp); if (order_for_deterministic_push(e, e->species[sp])) return 1; return push_timing_hinted(e, e->species[sp]); }
+int vpic_hip_advance_p(vpic_hip_engine_t *e, int sp) {
+  ENGINE(e); SPECIES(e, sp);
+  Species &s = e->species[sp];
+  if (!s.phase_pending) s.nm = 0;                      // (this push begins a new mover list: what was left on the old one is dropped before the species is ordered, not after)
+  if (order_for_deterministic_push(e, s)) return 1;
+  return push_timing_hinted(e, s);
+}
 int vpic_hip_advance_p_async(vpic_hip_engine_t *e, int sp) {
   ENGINE(e); SPECIES(e, sp);
   if (sp >= MAX_SPECIES) VH_FAIL("the device-resident exchange serves %d species", MAX_SPECIES);
@@ -764,6 +772,7 @@ static int sort_and_push(Engine *e, Species &s, bool may_fuse, const std::functi
 }
 int vpic_hip_sort_advance_p(vpic_hip_engine_t *e, int sp) {
   ENGINE(e); SPECIES(e, sp);
+  if (!e->species[sp].phase_pending) e->species[sp].nm = 0;      // (as vpic_hip_advance_p: the push begins a new mover list)
   return sort_and_push(e, e->species[sp], true, [](Species &) { return 0; });
 }
 int vpic_hip_energy_p(vpic_hip_engine_t *e, int sp, double *energy) {
@@ -1227,6 +1236,7 @@ int vpic_hip_step(vpic_hip_engine_t *e, int64_t step, int sort_interval) {
     // plain launches measure 0-1.3 % slower.  VPIC_HIP_SORT_IN_PUSH=0 turns it off.
     // (... or before it, where that is cheaper: sort_and_push)
     pushed[k] = 1;
+    s.nm = 0;                                            // (this push begins a new mover list: movers no round of the last step served are dropped before the species is ordered, not after)
     auto hints = [&](Species &sp) -> int {
       // the next step sorts this species: let this push count for that sort (push.hip, Species::hist)
       if (sort_interval > 0 && (step + 1) % sort_interval == 0 && wants_tile_order(e, sp)) sp.hist_request = true;

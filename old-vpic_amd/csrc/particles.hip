@@ -142,6 +142,11 @@ int k_load_maxwellian(Engine *e, Species &s, int ppc, unsigned seed, float q, fl
   hipLaunchKernelGGL(load_maxwellian_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, e->stream, s.p, e->gk,
                      ppc, (int)np, seed, q, ux, uy, uz, vth);
   VH_CHECK(hipGetLastError());
+  if (s.has_tags) {                                      // the species loses its tags, as in load_profile: whoever switches them on again finds zeros
+    VH_CHECK(hipMemsetAsync(s.tag, 0, sizeof(int64_t) * s.max_np, e->stream));
+    VH_CHECK(hipMemsetAsync(s.tag2, 0, sizeof(int64_t) * s.max_np, e->stream));
+    s.has_tags = false;
+  }
   s.np = np; s.nm = 0; s.partition_valid = false; s.tile_valid = false; s.n_holes = 0; s.hist_valid = false;
   s.q_max = std::max(s.q_max, fabsf(q));
   s.chargeless = q == 0.f;                             // tracer copies (decks/trecon-part/tracer.cxx:64-70): nothing to deposit
@@ -559,6 +564,10 @@ __global__ void clear_word_kernel(unsigned *__restrict__ w) { *w = 0; }
 __global__ void publish_word_kernel(unsigned *__restrict__ host_word, const unsigned *__restrict__ dev_word) { *host_word = *dev_word; }
 
 int k_sort_p(Engine *e, Species &s, bool tile_order, bool may_fuse) {
+  // a mover names its particle by array index: nothing is reordered under a pending one (checked before anything is touched)
+  if (s.nm > 0 || s.phase_pending)
+    VH_FAIL("sort_p: the species has %lld pending movers%s: a sort would move the particles they name", (long long)s.nm,
+            s.phase_pending ? " and the second phase of its push still to run" : "");
   const TileK tk = make_tile_k(e->gk);
   const int n1 = (tile_order ? tk.ntiles * TILE_CELLS : e->gk.nv) + 1;
   // by tile only or by cell within a tile, inside the push that follows, which count (policy.h: plan_sort)
